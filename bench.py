@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the MAP deconvolution inner loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N = 1)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]          (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline and nothing else: set-up, W warm-up steps, the settle steps, ONE timed region of
+exactly K steps, the result line.  `--full` adds everything else described below (the untimed kernel-timer phase, clock
+probes, rooflines, the side runs with other convolution methods / sizes / schedules, the CPU baseline) and times the
+headline over `--repeats` (default 9) regions.  `--dump-outputs DIR` writes what the last timed step computed -- the
+flux of every component and the loss scalars, as a caller of the fit receives them -- as DIR/<name>.npy.
 
 Workload (BASELINE.json `metric`, configs[2], inputs as SURVEY.md section 8(d) specifies them): 2048x2048 image, 8
 synthetic observations with varying PSF (Gaussian, sigma = 1.5 + 0.25 i, on 17x17 arrays and -- sigma >= 3: observations 6
@@ -16,24 +22,26 @@ prior bands, the fused chain rule + Adam update.  The convolution method is "aut
 benchmark's Gaussian PSFs are rank 1, so the headline runs the separable strip-walk kernels (the PSFs of both sizes share
 one plan and one batched step: forward launch = convolution + Poisson pass of all local observations); the same fit
 with the PSFs treated as general kernels (MFMA direct convolution up to 17 taps, native FFT beyond: `general_psf`) and through the FFT path (`fft_psf`,
-the path the north star names: the native FFT convolution of csrc/fftnative.hip on these sizes) is timed beside it, and
-so is `c6_chandra_like` (calibrations + up-sampling x2 + general 65x65 PSFs: the reference's Chandra example).
+the path the north star names: the native FFT convolution of csrc/fftnative.hip on these sizes) is timed beside it with
+--full, and so is `c6_chandra_like` (calibrations + up-sampling x2 + general 65x65 PSFs: the reference's Chandra example).
 Total work is fixed as N grows (observations round-robin over the ranks, the prior split by patch
 rows): strong scaling.  All inputs are resident in HBM before the timed region.
 
-Timing protocol: W warm-up steps, then a settle phase of at least 0.3 s of steps (`settle`, its own field: clocks and
-caches reach their sustained state), then R = `--repeats` timed regions of EXACTLY K steps each, every one bracketed by
-barrier + synchronize and reduced by MAX over the ranks; `ms_per_step` / `value` are the MEDIAN region (min and max are
-reported beside it).  The kernel timers (hipEvent pairs recorded by the library around every launch, on the launch
+Timing protocol: W warm-up steps, then a settle phase (`settle`, its own field: clocks and caches reach their sustained
+state; `--settle-steps`, default 500 = about 0.3 s of the headline's steps) that runs until W + settle-steps epochs have
+run whatever the "auto" policy's probe took -- so every run starts its timed steps from the same state --, then
+R = `--repeats` timed regions of EXACTLY K steps each (plain run: R = 1), every one bracketed by barrier + synchronize
+and reduced by MAX over the ranks; `ms_per_step` / `value` are the MEDIAN region (min and max are reported beside it).
+With --full the kernel timers (hipEvent pairs recorded by the library around every launch, on the launch
 stream) run in a separate, untimed phase of >= 16 steps after the timed regions, so they neither perturb the timed
 steps nor rest on two samples.  `clock_mhz` is the shader clock the device holds under a vector-ALU load on every CU
 (jd_clock_probe): boards differ by several percent, and the line says which one it was measured on.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel of the step (the fp16 screen of the
+Prints ONE JSON line (rank 0).  With --full, `roofline` describes the dominant kernel of the step (the fp16 screen of the
 GMM arg-max: matrix-core roof; `roofline_section8d` prices the whole GMM forward pass by SURVEY section 8(d)'s
 dense fp32 definition), `roofline_poisson` the fused Poisson pass (HBM roof), `roofline_fft` the five launches of one
 observation's likelihood step on the native FFT convolution (the FFT side run).  `--config c2|c4|c5` run the other BASELINE configurations (parity-test cases; the default c3
-is the one the metric is quoted on).  `cpu_baseline` times oracle/cpu_ref.py (the PyTorch-CPU restatement of the
+is the one the metric is quoted on).  `cpu_baseline` (--full) times oracle/cpu_ref.py (the PyTorch-CPU restatement of the
 reference) on a bounded sample on rank 0 at N = 1.
 """
 import argparse
@@ -67,7 +75,10 @@ FP32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 =
 F16_MATRIX_PEAK_TFLOPS = 2516.6  # 16 x the fp32 rate: v_mfma_f32_32x32x16_f16, dense (MI355X_MICROARCH.md: ~2.5 PF)
 PATCH, D, STRIDE = 8, 64, 4
 PROFILE_STEPS = 16  # steps of the untimed profile phase: every launch of every one of them is bracketed by a hipEvent pair
-SETTLE_SECONDS = 0.3
+# settle steps: about 0.3 s of the headline's steps, and more than the "auto" policy's probe and trial ever take
+# (warm_policy's cap), so that the epoch count before the timed steps never depends on what the policy decided
+SETTLE_STEPS = 500
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: all files together
 
 
 def build_session(cfg_name, device, seed=0, dist=None, fit_mode="joint", shared_psf=False):
@@ -187,22 +198,27 @@ def c6_roofline(plan, counts_shape, n_obs, u, kernel_ms):
             "note": "PMC traffic of these kernels: profiles/r05/pmc_hbm_traffic.csv rows c6"}
 
 
-def c6_run(device, dist_ctx, steps=20, warmup=3, repeats=3, shape=(2048, 2048), n_obs=8):
-    """Time config c6 (see `build_session_c6`): it/s, the per-kernel table and `roofline_c6` (the six launches of one
-    observation's likelihood step against the HBM roof)."""
+def c6_run(device, dist_ctx, steps=20, warmup=3, repeats=3, shape=(2048, 2048), n_obs=8, settle_steps=SETTLE_STEPS,
+           full=True, dump_dir=None):
+    """Time config c6 (see `build_session_c6`): it/s and, with `full`, the per-kernel table and `roofline_c6` (the six
+    launches of one observation's likelihood step against the HBM roof)."""
     session = build_session_c6(device, shape=shape, n_obs=n_obs)
-    for _ in range(max(warmup, 10)):
-        session.epoch()
-    warm_policy(session)  # (the "auto" policy's probe and trial epochs)
-    torch.cuda.synchronize(device)
-    stats = region_stats(timed_regions(session, steps, repeats, device, dist_ctx), steps)
+    gc.collect()  # (before the warm-up: see `main`)
+    gc.disable()
+    try:
+        warm_up(session, device, dist_ctx, max(warmup, 10), settle_steps)
+        stats = region_stats(timed_regions(session, steps, repeats, device, dist_ctx, collect=False), steps)
+    finally:
+        gc.enable()
     host_ms = 1e3 * float(np.median(HOST_ENQUEUE[-1])) / steps
     replayed = bool(getattr(session, "_graphs", None))
-    prof = profile_phase(session, device, n_obs, steps=4)
+    scal = session.scalars.detach().cpu().numpy()
+    if dump_dir is not None:
+        dump_outputs(dump_dir, session_outputs(session))
+    prof = profile_phase(session, device, n_obs, steps=4) if full else {}
     nested = ("gmm_stage", "gmm_screen", "gmm_sort", "gmm_exact")
     models = session.total_loss.poisson_loss.npred_models_all
     plan = models[0].plan
-    scal = session.scalars.detach().cpu().numpy()
     if not np.all(np.isfinite(scal)):
         raise SystemExit(f"c6: non-finite losses {scal}")
     out = {
@@ -218,15 +234,16 @@ def c6_run(device, dist_ctx, steps=20, warmup=3, repeats=3, shape=(2048, 2048), 
         # library runs its per-dataset launches (measured faster there)
         "batched_calibrated_entry": bool(getattr(session, "batch_joint_calibrated", False)),
         "graph_policy": getattr(session, "graph_policy", None), "epochs_replayed_from_graphs": replayed,
-        "kernel_ms_per_step": {k: v[0] / 4 for k, v in prof.items() if v[1] and k not in nested},
-        "launches_per_step": {k: v[1] / 4 for k, v in prof.items() if v[1] and k not in nested},
     }
-    out["roofline_c6"] = c6_roofline(plan, shape, n_obs, 2, out["kernel_ms_per_step"])
+    if full:
+        out["kernel_ms_per_step"] = {k: v[0] / 4 for k, v in prof.items() if v[1] and k not in nested}
+        out["launches_per_step"] = {k: v[1] / 4 for k, v in prof.items() if v[1] and k not in nested}
+        out["roofline_c6"] = c6_roofline(plan, shape, n_obs, 2, out["kernel_ms_per_step"])
     del session
     return out
 
 
-def e0102_run(device, n_epochs=250, shape=(256, 256), n_obs=24, psf_shape=(128, 128), K=128):
+def e0102_run(device, n_epochs=250, shape=(256, 256), n_obs=24, psf_shape=(128, 128), K=128, dump_dir=None):
     """Time-to-solution of the fit the reference publishes a runtime for (examples/chandra-e0102-filament.py:91-93,178-222:
     24 Chandra observations of one field, 128x128 MARX PSFs, ``upsampling_factor=2``, one `NPredCalibration` per
     observation, GMM patch prior, ``n_epochs=250`` in the reference's own SEQUENTIAL mode -- "takes about 30 min on an M1
@@ -263,6 +280,10 @@ def e0102_run(device, n_epochs=250, shape=(256, 256), n_obs=24, psf_shape=(128, 
     totals = np.asarray(result.trace_loss["total"], dtype=np.float64)
     if not np.all(np.isfinite(totals)) or not np.all(np.isfinite(result.flux_total)):
         raise SystemExit("e0102: non-finite trace or flux")
+    if dump_dir is not None:
+        outputs = {f"flux_{name}": flux for name, flux in result.components.fluxes_numpy.items()}
+        outputs["trace_total"] = totals
+        dump_outputs(dump_dir, outputs)
     # the epochs alone (no set-up), eagerly enqueued against replayed: a session of the same fit
     comp, calibrations = build()
     session = MAPDeconvolver(n_epochs=1, display_progress=False, device=device, fit_mode="sequential").session(
@@ -454,25 +475,49 @@ def warm_policy(session, cap=128):
     return n
 
 
-def settle(session, device, dist_ctx, seconds=SETTLE_SECONDS, chunk=20):
-    """Steps for at least `seconds` before the timed regions (chunks of `chunk` steps; every rank runs the same number:
-    the ranks agree after each chunk whether all of them have had enough)."""
+def warm_up(session, device, dist_ctx, warmup, settle_steps=SETTLE_STEPS):
+    """The untimed epochs before the timed regions: `warmup` steps, the "auto" policy's probe and trial epochs (single
+    process), then settle steps until `warmup + settle_steps` epochs have run.  That count depends on the arguments alone
+    -- not on what the policy decided, nor on how fast the build is --, so the timed steps start from the same state in
+    every run (and on every rank).  Returns the `settle` field: the steps after the policy and their seconds."""
+    for _ in range(warmup):
+        session.epoch()
+    policy = warm_policy(session) if dist_ctx.world_size == 1 else 0
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
-    n = 0
-    while True:
-        for _ in range(chunk):
-            session.epoch()
-        n += chunk
-        torch.cuda.synchronize(device)
-        more = time.perf_counter() - t0 < seconds
-        if dist_ctx.world_size > 1:
-            t = torch.tensor([1.0 if more else 0.0], dtype=torch.float64, device=device)
-            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-            more = bool(t.item() > 0)
-        if not more:
-            break
-    return {"seconds": time.perf_counter() - t0, "steps": n}
+    n = max(settle_steps - policy, 0)
+    for _ in range(n):
+        session.epoch()
+    torch.cuda.synchronize(device)
+    return {"seconds": time.perf_counter() - t0, "steps": n, "policy_steps": policy}
+
+
+def session_outputs(session):
+    """What a caller of the fit receives after the last step: the flux of every component (counts grid) and the loss
+    scalars of that step [dataset losses | log-priors]."""
+    torch.cuda.synchronize()
+    outputs = {f"flux_{name}": flux for name, flux in session.components.fluxes_numpy.items()}
+    outputs["loss_scalars"] = session.scalars.detach().cpu().numpy()
+    return outputs
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write {name: array} as `directory`/<name>.npy in float32 (float64 stays float64), DUMP_BUDGET_BYTES in all.  The
+    small arrays are written whole; an array beyond its share of what is left is replaced by a fixed sample of its
+    elements (seeded: the same indices for the same shape in every run)."""
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    items = [(name, np.asarray(a)) for name, a in arrays.items()]
+    items = [(name, a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)) for name, a in items]
+    left = budget - 256 * len(items)  # (.npy headers)
+    for i, (name, a) in enumerate(sorted(items, key=lambda item: item[1].nbytes)):
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            pick = np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(directory / f"{name}.npy", a)
+        left -= a.nbytes
+    log(f"outputs written to {directory}: {', '.join(name for name, _ in items)}")
 
 
 HOST_ENQUEUE = []  # per call of timed_regions: seconds the host needs to enqueue a region's steps (MAX over the ranks)
@@ -482,13 +527,15 @@ HOST_ENQUEUE = []  # per call of timed_regions: seconds the host needs to enqueu
 ENQUEUE_BURST = 16
 
 
-def timed_regions(session, steps, repeats, device, dist_ctx):
+def timed_regions(session, steps, repeats, device, dist_ctx, collect=True):
     """`repeats` regions of exactly `steps` steps, each bracketed by barrier + synchronize; per region the MAX over the
-    ranks.  Returns the list of region times in seconds."""
+    ranks.  Returns the list of region times in seconds.  `collect=False`: the caller has run the cycle collector
+    before its settle steps (see `main`)."""
     times, enqueue = [], []
     # Python's cycle collector stays out of the timed steps: when it frees the device buffers of an earlier session
     # (set-up objects, a side run) inside the loop, every hipFree synchronises the device
-    gc.collect()
+    if collect:
+        gc.collect()
     gc.disable()
     try:
         for _ in range(repeats):
@@ -539,9 +586,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=9, help="timed regions of --steps steps each; the median is reported")
-    ap.add_argument("--settle-seconds", type=float, default=SETTLE_SECONDS,
-                    help="steps run for at least this long between the warm-up and the timed regions (0: none)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default: 1, with --full 9)")
+    ap.add_argument("--settle-steps", type=int, default=SETTLE_STEPS,
+                    help="untimed steps between the warm-up and the timed regions, the 'auto' policy's included (0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: kernel timers, clock probes, rooflines, the side runs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (component fluxes, loss scalars) as DIR/<name>.npy")
     ap.add_argument("--config", default="c3", choices=sorted(c for c in CONFIGS if c != "c3odd") + ["c6", "e0102"])
     ap.add_argument("--epochs", type=int, default=250, help="--config e0102: epochs of the sequential fit")
     ap.add_argument("--no-c6", action="store_true", help="skip the c6 side run (calibrations + up-sampling + general 65x65 PSFs)")
@@ -554,6 +606,8 @@ def main():
                          "times every rank of N = 2 / 4 / 8 that way")
     ap.add_argument("--rank", type=int, default=0, help="with --shard-of N: the rank whose share is timed")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an AMD GPU (libjolideco_hip.so has no CPU fallback)")
@@ -579,13 +633,14 @@ def main():
         if world != 1:
             raise SystemExit("--config e0102 is a single-GPU run (sequential mode: replicas only)")
         log("e0102: time to solution of the reference's Chandra example shape")
-        print(json.dumps(e0102_run(device, n_epochs=args.epochs)))
+        print(json.dumps(e0102_run(device, n_epochs=args.epochs, dump_dir=args.dump_outputs)))
         return
     if args.config == "c6":
         if world != 1:
             raise SystemExit("--config c6 is a single-GPU side run")
         log("c6: calibrations + up-sampling x2 + general 65x65 PSFs")
-        out = c6_run(device, dist_ctx, steps=max(args.steps // 10, 5), warmup=max(args.warmup // 5, 2), repeats=min(args.repeats, 3))
+        out = c6_run(device, dist_ctx, steps=max(args.steps // 10, 5), warmup=max(args.warmup // 5, 2), repeats=min(args.repeats, 3),
+                     settle_steps=args.settle_steps, full=args.full, dump_dir=args.dump_outputs)
         out = dict({"metric": "MAP iters/sec (c6)", "n_gpus": 1, "higher_is_better": True, "dtype": "f32", "data": "synthetic",
                     "scaling": "strong", "vs_baseline": None, "warmup": max(args.warmup // 5, 2), "config": {"workload": out.pop("workload")}}, **out)
         print(json.dumps(out))
@@ -605,41 +660,47 @@ def main():
     torch.cuda.synchronize(device)
     log("session ready; warm-up")
 
-    for _ in range(args.warmup):
-        session.epoch()
-    if dist_ctx.world_size == 1:
-        warm_policy(session)  # (a single-process fit's "auto" policy: its probe and trial epochs are not timed)
-    torch.cuda.synchronize(device)
-    settled = settle(session, device, dist_ctx, args.settle_seconds) if args.settle_seconds > 0 else {"seconds": 0.0, "steps": 0}
-    log(f"settled: {settled['steps']} steps in {settled['seconds']:.3f} s; timed regions")
-    times = timed_regions(session, args.steps, max(args.repeats, 1), device, dist_ctx)
+    # The cycle collector runs BEFORE the warm-up, not between the settle steps and the timed region: the device idles
+    # while it runs (~70 ms), and the region that follows such a pause is ~1.5 % slower than the ones after it
+    gc.collect()
+    gc.disable()
+    try:
+        # (a single-process fit's "auto" policy: its probe and trial epochs are not timed)
+        settled = warm_up(session, device, dist_ctx, args.warmup, args.settle_steps)
+        log(f"settled: {settled['policy_steps']} + {settled['steps']} steps in {settled['seconds']:.3f} s; timed regions")
+        times = timed_regions(session, args.steps, max(args.repeats, 1), device, dist_ctx, collect=False)
+    finally:
+        gc.enable()
     stats = region_stats(times, args.steps)
     host_enqueue_ms = 1e3 * float(np.median(HOST_ENQUEUE[-1])) / args.steps
     replayed, graph_policy = bool(getattr(session, "_graphs", None)), getattr(session, "graph_policy", None)
     elapsed = args.steps / stats["value"]  # the median region
     log(f"timed regions done: {stats['ms_per_step']:.4f} ms/step (median of {len(times)}; "
         f"{stats['ms_per_step_min']:.4f} .. {stats['ms_per_step_max']:.4f})")
-    clock_mhz = _hip.clock_probe(2.0, device)
     # numerics of the run itself: the loss scalars after the last TIMED step (before the untimed profile phase)
     torch.cuda.synchronize(device)
     scal = session.scalars.detach().cpu().numpy()
-    epochs_run = args.warmup + settled["steps"] + args.steps * len(times)
-    if world > 1:
-        session.comm_events = []
-    prof = profile_phase(session, device, n_obs)
-    comm_ms = session.comm_times_ms() if world > 1 else None
-    session.comm_events = None
-    # the shader clock INSIDE the screen kernel (round-4 verdict item 6): an untimed phase on the stamped instantiation of
-    # the kernel (jd_gmm_screen_clock) -- s_memtime / s_memrealtime ticks of up to 4096 blocks per launch
-    screen_clock = None
-    handles = [p.gmm.handle(device) for p in session.priors if hasattr(p, "gmm")]
-    if handles and world == 1 and args.shard_of <= 1:
-        handles[0].screen_clock()  # arms the handle
-        session.reset_graphs()
-        for _ in range(max(args.warmup, 8)):
-            session.epoch()
-        mhz, samples = handles[0].screen_clock()
-        screen_clock = {"mhz": mhz, "blocks_sampled": samples} if samples else None
+    epochs_run = args.warmup + settled["policy_steps"] + settled["steps"] + args.steps * len(times)
+    if args.dump_outputs and dist_ctx.rank == 0:
+        dump_outputs(args.dump_outputs, session_outputs(session))
+    if args.full:
+        clock_mhz = _hip.clock_probe(2.0, device)
+        if world > 1:
+            session.comm_events = []
+        prof = profile_phase(session, device, n_obs)
+        comm_ms = session.comm_times_ms() if world > 1 else None
+        session.comm_events = None
+        # the shader clock INSIDE the screen kernel (round-4 verdict item 6): an untimed phase on the stamped instantiation
+        # of the kernel (jd_gmm_screen_clock) -- s_memtime / s_memrealtime ticks of up to 4096 blocks per launch
+        screen_clock = None
+        handles = [p.gmm.handle(device) for p in session.priors if hasattr(p, "gmm")]
+        if handles and world == 1 and args.shard_of <= 1:
+            handles[0].screen_clock()  # arms the handle
+            session.reset_graphs()
+            for _ in range(max(args.warmup, 8)):
+                session.epoch()
+            mhz, samples = handles[0].screen_clock()
+            screen_clock = {"mhz": mhz, "blocks_sampled": samples} if samples else None
 
     # sanity: the fit must have produced finite numbers
     if not np.all(np.isfinite(scal)):
@@ -651,6 +712,74 @@ def main():
         return
 
     ms_per_step = 1e3 * elapsed / args.steps
+    # PSF array sizes of the observations as SURVEY.md section 8(d) gives them (17x17; 33x33 for sigma >= 3)
+    from jolideco_amd.data import psf_shape
+
+    psf_shapes = ["%dx%d" % psf_shape(1.5 + 0.25 * i) for i in range(n_obs)]
+    runs = []
+    for shp in psf_shapes:
+        if runs and runs[-1][0] == shp:
+            runs[-1][1] += 1
+        else:
+            runs.append([shp, 1])
+    psf_sizes = " + ".join(f"{n} x {shp}" for shp, n in runs)
+    models_all = session.total_loss.poisson_loss.npred_models_all
+    methods = sorted({m.plan.method for m in models_all})
+    out = {
+        "metric": ("MAP iters/sec at 2048x2048, 8-obs joint fit" if args.config == "c3" else f"MAP iters/sec ({args.config})")
+        + (f" [TUNING: rank {args.rank} of {args.shard_of}, no collective]" if args.shard_of > 1 else ""),
+        "value": args.steps / elapsed,
+        "unit": "iters/s",
+        "n_gpus": world,
+        "distributed": dist_info,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "ms_per_step_min": stats["ms_per_step_min"], "ms_per_step_max": stats["ms_per_step_max"],
+        # time the HOST needs to issue one step (python + ctypes + hipLaunch / hipGraphLaunch, and at N > 1 the
+        # torch.distributed calls): over the first ENQUEUE_BURST steps of a timed region, issued into an empty queue;
+        # median region, MAX over the ranks.  A step cannot be faster than this: where it approaches ms_per_step the run
+        # is host bound
+        "host_enqueue_ms_per_step": host_enqueue_ms,
+        # the timed steps were replayed from captured hipGraphs (device-resident step scalars, jolideco_amd/core.py)
+        "epochs_replayed_from_graphs": replayed,
+        # what the session's "auto" policy decided after its probe epochs (jolideco_amd/core.py: captured epochs only
+        # where the host bounds the fit)
+        "graph_policy": graph_policy,
+        "repeats": len(times), "timing": "median of `repeats` regions of `steps` steps, each bracketed by barrier + synchronize",
+        "settle": settled,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": ("c1: 128x128, one point-source observation (1000 counts at the centre, Gaussian PSF sigma 3 on 17x17, "
+                         "exposure 1, background 2), uniform prior, the reference's sequential loop (one step + one trace "
+                         "evaluation per epoch), Adam lr 0.1" if args.config == "c1" else
+                         f"{args.config}: {H}x{W}, {n_obs} observations (Gaussian PSFs sigma = 1.5 + 0.25 i on {psf_sizes}, "
+                         f"varying exposure/background), GMM patch prior 8x8 stride 4 K={K}, joint fit, Adam lr 0.1"),
+            "psf_shapes": psf_shapes,
+            "global_observations": n_obs,
+            "sharding": (f"observations over {world} rank(s) by estimated cost (longest processing time first), prior by patch "
+                         "rows in shares that even the ranks out; per step 1 all-reduce of the "
+                         "likelihood gradient started before the prior and overlapped with it + 1 all-gather of the prior "
+                         "bands" if os.environ.get("JOLIDECO_DIST_OVERLAP", "1") != "0" else
+                         f"observations over {world} rank(s) by estimated cost, prior by patch rows, 1 all-reduce/step")
+            if world > 1 else "single GPU",
+            # which convolution the fit used: Gaussian PSFs are rank 1, so "auto" takes the separable kernel
+            "conv_method": "+".join(methods),
+        },
+        # numerics of the run itself: the loss scalars of the last timed step [dataset losses | log-priors] -- the same
+        # for any number of ranks (tests/test_gpu_distributed.py compares a 2-rank run with a single process)
+        "check": {"epochs_run": epochs_run, "scalars_last_step": [float(v) for v in scal]},
+    }
+    if not args.full:
+        print(json.dumps(out))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+
     n_py, n_px = (H - PATCH) // STRIDE + 1, (W - PATCH) // STRIDE + 1
     shares = getattr(session, "prior_shares", None)  # (cost-aware placement: a rank with costly datasets takes fewer rows)
     rows = dist_ctx.shard_range(n_py, shares) if world > 1 else (0, n_py)
@@ -716,8 +845,6 @@ def main():
     # (`sep_conv_kernel<.., POISSON>`): flux, exposure, background, counts in; g out = 20 B/pixel, and the convolution
     # image (4 B/pixel written + 4 read back) never exists.
     poi_ms, poi_n = avg_ms("poisson_fused")
-    models_all = session.total_loss.poisson_loss.npred_models_all
-    methods = sorted({m.plan.method for m in models_all})
     n_comp = len(session.components)
     # batched joint step: ONE launch covers all local datasets (jd_npred_poisson_batch_[multi_]fwd_bwd)
     batched = bool(getattr(session, "batch_joint", False))
@@ -776,65 +903,9 @@ def main():
     dominant = max(kernel_ms_per_step, key=kernel_ms_per_step.get) if kernel_ms_per_step else None
     roofline = roof_poi if dominant == "poisson_fused" else roof_gmm
 
-    # PSF array sizes of the observations as SURVEY.md section 8(d) gives them (17x17; 33x33 for sigma >= 3)
-    from jolideco_amd.data import psf_shape
-
-    psf_shapes = ["%dx%d" % psf_shape(1.5 + 0.25 * i) for i in range(n_obs)]
-    runs = []
-    for shp in psf_shapes:
-        if runs and runs[-1][0] == shp:
-            runs[-1][1] += 1
-        else:
-            runs.append([shp, 1])
-    psf_sizes = " + ".join(f"{n} x {shp}" for shp, n in runs)
-    out = {
-        "metric": ("MAP iters/sec at 2048x2048, 8-obs joint fit" if args.config == "c3" else f"MAP iters/sec ({args.config})")
-        + (f" [TUNING: rank {args.rank} of {args.shard_of}, no collective]" if args.shard_of > 1 else ""),
-        "value": args.steps / elapsed,
-        "unit": "iters/s",
-        "n_gpus": world,
-        "distributed": dist_info,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "ms_per_step_min": stats["ms_per_step_min"], "ms_per_step_max": stats["ms_per_step_max"],
-        # time the HOST needs to issue one step (python + ctypes + hipLaunch / hipGraphLaunch, and at N > 1 the
-        # torch.distributed calls): over the first ENQUEUE_BURST steps of a timed region, issued into an empty queue;
-        # median region, MAX over the ranks.  A step cannot be faster than this: where it approaches ms_per_step the run
-        # is host bound
-        "host_enqueue_ms_per_step": host_enqueue_ms,
-        # the timed steps were replayed from captured hipGraphs (device-resident step scalars, jolideco_amd/core.py)
-        "epochs_replayed_from_graphs": replayed,
-        # what the session's "auto" policy decided after its probe epochs (jolideco_amd/core.py: captured epochs only
-        # where the host bounds the fit)
-        "graph_policy": graph_policy,
-        "repeats": len(times), "timing": "median of `repeats` regions of `steps` steps, each bracketed by barrier + synchronize",
-        "settle": settled,
+    out.update({
         "clock_mhz": clock_mhz,
         "kernel_profile_steps": PROFILE_STEPS,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": ("c1: 128x128, one point-source observation (1000 counts at the centre, Gaussian PSF sigma 3 on 17x17, "
-                         "exposure 1, background 2), uniform prior, the reference's sequential loop (one step + one trace "
-                         "evaluation per epoch), Adam lr 0.1" if args.config == "c1" else
-                         f"{args.config}: {H}x{W}, {n_obs} observations (Gaussian PSFs sigma = 1.5 + 0.25 i on {psf_sizes}, "
-                         f"varying exposure/background), GMM patch prior 8x8 stride 4 K={K}, joint fit, Adam lr 0.1"),
-            "psf_shapes": psf_shapes,
-            "global_observations": n_obs,
-            "sharding": (f"observations over {world} rank(s) by estimated cost (longest processing time first), prior by patch "
-                         "rows in shares that even the ranks out; per step 1 all-reduce of the "
-                         "likelihood gradient started before the prior and overlapped with it + 1 all-gather of the prior "
-                         "bands" if os.environ.get("JOLIDECO_DIST_OVERLAP", "1") != "0" else
-                         f"observations over {world} rank(s) by estimated cost, prior by patch rows, 1 all-reduce/step")
-            if world > 1 else "single GPU",
-        },
-        # numerics of the run itself: the loss scalars of the last timed step [dataset losses | log-priors] -- the same
-        # for any number of ranks (tests/test_gpu_distributed.py compares a 2-rank run with a single process)
-        "check": {"epochs_run": epochs_run, "scalars_last_step": [float(v) for v in scal]},
         "roofline": roofline,
         "roofline_poisson": roof_poi,
         # SURVEY section 8(d)'s own definition for the GMM prior: Np K (2 D^2 + 4 D) fp32 flop over the duration of the
@@ -849,14 +920,12 @@ def main():
         },
         "kernel_ms_per_step": kernel_ms_per_step,
         "dominant_kernel": dominant,
-    }
+    })
     if comm_ms is not None:
         # rank 0's compute stream, per step: time between enqueueing the wait for the all-reduce that was started before
         # the prior and its completion (what the overlap did NOT hide), the all-gather of the prior bands, or the one
         # blocking all-reduce of the non-overlapped schedule
         out["comm_ms_per_step"] = comm_ms
-    # which convolution the fit used: Gaussian PSFs are rank 1, so "auto" takes the separable kernel
-    out["config"]["conv_method"] = "+".join(methods)
     # convolution kernel, HBM bound: forward reads flux + exposure and writes the convolution (12 B/pixel), the
     # adjoint reads g + exposure + the gradient accumulator and writes it back (16 B/pixel): 14 B/pixel on average
     conv_key = "sep_conv" if "sep_conv" in kernel_ms_per_step else "direct_conv" if "direct_conv" in kernel_ms_per_step else None

@@ -9,6 +9,7 @@ of the loads"):
 import re
 import subprocess
 import sys
+import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -16,10 +17,13 @@ FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -mllvm -a
 
 
 def scan(src):
-    out = Path("/tmp") / (src.stem + ".isa_loads.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, str(src), "-o", str(out)], cwd=src.parent, capture_output=True, check=True)
+    # (a directory of this call's own: a fixed path is shared with other users and with concurrent runs)
+    with tempfile.TemporaryDirectory(prefix="isa_loads-") as tmp:
+        out = Path(tmp) / (src.stem + ".s")
+        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, str(src), "-o", str(out)], cwd=src.parent, capture_output=True, check=True)
+        text = out.read_text()
     name, rows = None, []
-    for line in out.read_text().split("\n"):
+    for line in text.split("\n"):
         m = re.match(r"^(_Z\S+):", line)
         if m:
             name, loads, full, flat_ld, flat_st = m.group(1), 0, 0, 0, 0

@@ -8,14 +8,14 @@ R=${1:-r05}
 OUT=gpurun_out/profile_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-python3 bench.py > $OUT/c3_n1_bench.json 2> $OUT/c3_n1_bench.err
-python3 bench.py --steps 20 --warmup 5 > $OUT/c3_n1_bench_driver_flags.json 2>> $OUT/c3_n1_bench.err
+python3 bench.py --full > $OUT/c3_n1_bench.json 2> $OUT/c3_n1_bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/c3_n1_bench_driver_flags.json 2>> $OUT/c3_n1_bench.err
 for cfg in c2 c4 c5; do
-  python3 bench.py --config $cfg --steps 100 --warmup 10 > $OUT/${cfg}_n1_bench.json 2> $OUT/${cfg}_n1_bench.err
+  python3 bench.py --full --config $cfg --steps 100 --warmup 10 > $OUT/${cfg}_n1_bench.json 2> $OUT/${cfg}_n1_bench.err
 done
-python3 bench.py --config c6 > $OUT/c6_n1_bench.json 2> $OUT/c6_n1_bench.err
-python3 bench.py --config c1 --steps 200 --warmup 20 > $OUT/c1_n1_bench.json 2> $OUT/c1_n1_bench.err
-python3 bench.py --config e0102 > $OUT/e0102_bench.json 2> $OUT/e0102_bench.err
+python3 bench.py --full --config c6 > $OUT/c6_n1_bench.json 2> $OUT/c6_n1_bench.err
+python3 bench.py --full --config c1 --steps 200 --warmup 20 > $OUT/c1_n1_bench.json 2> $OUT/c1_n1_bench.err
+python3 bench.py --full --config e0102 > $OUT/e0102_bench.json 2> $OUT/e0102_bench.err
 python3 tools/gpu/small_fits.py > $OUT/small_fits.txt 2>&1
 python3 tools/rccl_probe.py > $OUT/rccl_probe.json 2> $OUT/rccl_probe.err
 # (the profiler runs below time the by-value epochs: the same kernels, no graph replay under the tracer)
@@ -23,7 +23,7 @@ export JOLIDECO_GRAPH=0 JOLIDECO_STEP_SCALARS=host
 kernel_stats() {  # <label> <bench args...>: rocprofv3 kernel statistics of one bench command
   local label=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$label -o $label -- \
-      python3 bench.py "$@" --steps 20 --warmup 5 --no-cpu-baseline --no-general-psf > $OUT/prof_$label.log 2>&1
+      python3 bench.py --full "$@" --steps 20 --warmup 5 --no-cpu-baseline --no-general-psf > $OUT/prof_$label.log 2>&1
   local stats
   stats=$(find $OUT/prof_$label -name "*kernel_stats.csv" | sort | sed -n 1p)
   [ -n "$stats" ] && [ -s "$stats" ] || { echo "no kernel_stats.csv for $label" >&2; exit 1; }
@@ -33,7 +33,7 @@ traffic() {  # <label> <bench args...>: FETCH_SIZE and WRITE_SIZE per kernel, se
   local label=$1; shift
   for counter in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --pmc $counter --output-format csv -d $OUT/pmc_${label}_$counter -o pmc -- \
-        python3 bench.py "$@" --steps 5 --warmup 2 --repeats 1 --settle-seconds 0 --no-cpu-baseline --no-general-psf \
+        python3 bench.py --full "$@" --steps 5 --warmup 2 --repeats 1 --settle-steps 0 --no-cpu-baseline --no-general-psf \
         > $OUT/pmc_${label}_$counter.log 2>&1
   done
   python3 tools/pmc_traffic_csv.py ${label} $OUT/pmc_${label}_FETCH_SIZE $OUT/pmc_${label}_WRITE_SIZE > $OUT/pmc_${label}.csv
@@ -51,7 +51,7 @@ unset JOLIDECO_CONV_METHOD
 sq_pass() {
   local name=$1; shift
   rocprofv3 --pmc "$@" --output-format csv -d $OUT/sq_$name -o pmc -- \
-      python3 bench.py --steps 5 --warmup 2 --repeats 1 --settle-seconds 0 --no-cpu-baseline --no-general-psf > $OUT/sq_$name.log 2>&1
+      python3 bench.py --full --steps 5 --warmup 2 --repeats 1 --settle-steps 0 --no-cpu-baseline --no-general-psf > $OUT/sq_$name.log 2>&1
 }
 sq_pass a SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU
 sq_pass b SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE
