@@ -159,6 +159,32 @@ int jd_npred_poisson_fwd_bwd(jd_conv_plan* plan, int n_comp, const float* const*
                              float eps, float* loss_out, float* const* grad_flux, int accumulate,
                              float grad_scale, float* npred_out, int upsampling, void* stream);
 
+/* The same step for ONE dataset whose n_comp flux components live on grids of DIFFERENT up-sampling factors
+ * (`upsampling_factor` is an attribute of each SpatialFluxComponent, and NPredModels.from_dataset_numpy builds one
+ * NPredModel per component with that component's factor, models/npred.py:279-295): component c has its own plan on the
+ * (Hc * u_c, Wc * u_c) grid, (Hc, Wc) the counts grid, and its own factor u_c >= 1.
+ *   pooled_c      = sumpool_{u_c}( PSF_c (*) (flux_c x E_c) )                        models/npred.py:160-191
+ *   n             = sum_c max(pooled_c, 0) + background                              models/npred.py:241-261
+ *   loss_out     <- mean(n - c*log(n+eps)) + stirling_mean                           loss.py:35-37
+ *   grad_flux[c] <- (accumulate ? += : =) grad_scale * E_c * corr(PSF_c, replicate_{u_c}( g * [pooled_c >= 0] )),
+ *                   g = (1 - c/(n+eps)) / (Hc*Wc)
+ * Every component's convolution and adjoint run on that component's plan by the plan's own method (separable, direct,
+ * native FFT, rocFFT); between them ONE launch over the counts grid reads component c's convolution with plan c's row
+ * pitch, crop offset and factor, sum-pools, clips per component, adds the background, accumulates the loss, writes
+ * npred_out and writes the masked, u_c x u_c-replicated g straight into plan c's adjoint input.
+ *   plans, flux, exposure, khat, grad_flux, upsampling : host arrays of n_comp entries (grad_flux nullable: forward
+ *                   only); flux[c], exposure[c], grad_flux[c] on plan c's grid; plans may repeat
+ *   background, counts, npred_out (nullable)           : on the counts grid
+ * Every plan's image shape must be exactly upsampling[c] times one common counts shape, and every factor lies in
+ * [1, 8] as in jd_npred_poisson_fwd_bwd (JD_ERR_INVALID otherwise).
+ * The work buffers belong to the plans: after the first call with a set of plans the call neither allocates nor
+ * synchronises.  All other arguments as in jd_npred_poisson_fwd_bwd. */
+int jd_npred_poisson_mixed_fwd_bwd(jd_conv_plan* const* plans, int n_comp, const float* const* flux,
+                                   const float* const* exposure, const float* const* khat, const float* background,
+                                   const float* counts, float stirling_mean, float eps, float* loss_out,
+                                   float* const* grad_flux, int accumulate, float grad_scale, float* npred_out,
+                                   const int* upsampling, void* stream);
+
 /* The joint step over SEVERAL datasets in three launches instead of four per dataset (new: the reference has no joint
  * mode; this is the batched form of the loop `for dataset: jd_npred_poisson_fwd_bwd(..., accumulate = dataset > 0)` that
  * jolideco_amd's fit_mode="joint" runs, jolideco/core.py:214-229 being its per-dataset counterpart).  Restrictions: one
@@ -429,7 +455,8 @@ enum {
   JD_KERNEL_GMM_EXACT = 14,      /*   stage 3: exact fp32 MFMA evaluation of the survivors (inside GMM_FWD) */
   JD_KERNEL_GMM_STAGE = 15,      /*   stage 0: patches -> mean-subtracted fp16 fragments, norms, scales (inside GMM_FWD) */
   JD_KERNEL_SHIFT = 16,          /* calibration: bilinear sub-pixel shift and its transpose (+ shift gradient partial sums) */
-  JD_KERNEL_COUNT = 17
+  JD_KERNEL_POISSON_MIXED = 17,  /* K3 for components of different up-sampling factors: pool + clip + NLL + replicated gradient */
+  JD_KERNEL_COUNT = 18
 };
 int jd_profile_enable(int capacity);
 int jd_profile_disable(void);

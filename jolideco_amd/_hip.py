@@ -50,6 +50,11 @@ EXPORTS = {
         [c_void_p, c_int, fpp, fpp, fpp, c_void_p, c_void_p, c_float, c_float, c_void_p, fpp, c_int, c_float,
          c_void_p, c_int, c_void_p],
     ),
+    "jd_npred_poisson_mixed_fwd_bwd": (
+        c_int,
+        [fpp, c_int, fpp, fpp, fpp, c_void_p, c_void_p, c_float, c_float, c_void_p, fpp, c_int, c_float, c_void_p,
+         POINTER(c_int), c_void_p],
+    ),
     "jd_npred_poisson_calibrated_fwd_bwd": (
         c_int,
         [c_void_p, c_int, fpp, fpp, fpp, c_void_p, c_void_p, c_float, c_float, c_void_p, fpp, c_int, c_float,
@@ -138,6 +143,7 @@ KERNEL_IDS = {
     "poisson_fused": 0, "gmm_fwd": 1, "gmm_bwd": 2, "gmm_gather": 3, "pad_mul": 4, "cmul": 5,
     "adjoint_epilogue": 6, "adam": 7, "fft_r2c": 8, "fft_c2r": 9, "direct_conv": 10, "sep_conv": 11,
     "gmm_screen": 12, "gmm_sort": 13, "gmm_exact": 14, "gmm_stage": 15, "shift": 16,
+    "poisson_mixed": 17,
 }
 
 _lib = None

@@ -520,6 +520,11 @@ class FitSession:
         names_all = list(datasets)
         # joint mode shards the datasets over the ranks; sequential mode runs full replicas
         self.prior_shares = None
+        if self.joint and dist.sharded and len({c.upsampling_factor or 1 for c in components.values()}) > 1:
+            raise NotImplementedError(
+                "a sharded joint fit (several ranks) with flux components of different upsampling_factor is not "
+                "implemented in jolideco_amd: run it in one process, or give all components one factor"
+            )
         if self.joint and dist.sharded:
             # cost-aware placement (identical on every rank): datasets by longest-processing-time-first on their estimated
             # cost, then the prior's patch rows in shares that top every rank up to the same estimated load

@@ -360,6 +360,217 @@ int launch_poisson_pooled(const PoissonArgs& a, int* n_partials, hipStream_t str
 int poisson_fused_max_partials(int Hp, int Wp) { return ((Wp + BLOCK - 1) / BLOCK) * Hp; }
 
 // ------------------------------------------------------------------------------------------
+// K3 for flux components of DIFFERENT up-sampling factors (jd_npred_poisson_mixed_fwd_bwd; models/npred.py:181-191,
+// 241-261): one pass over the COUNTS grid.  Component c's convolution lives in its own plan's buffer -- row pitch
+// Wp[c], crop offset (oy[c], ox[c]), factor up[c] -- and its gradient goes to that plan's adjoint input: the
+// up[c] x up[c] block of every counts pixel receives g, masked where the pooled value was clipped.
+// HBM bound: 4 * (2 + sum_c 2 up[c]^2) B per counts pixel with gradients.  Two components with factors 1..4 (the
+// diffuse + point-source fits) run an instantiation with both factors known at compile time: every load of a thread
+// is issued before the first one is consumed, and with VEC a thread takes TWO neighbouring counts pixels, so that a
+// row piece of its blocks is 2 up[c] floats -- loaded and stored as float4 (even factors) or float2 (odd ones).
+// Everything else (more components, larger factors) takes the generic kernel below.
+// ------------------------------------------------------------------------------------------
+template <int N, int V>
+__device__ __forceinline__ void load_piece(const float* __restrict__ p, float* out) {
+  if constexpr (V == 4) {
+#pragma unroll
+    for (int i = 0; i < N / 4; ++i) {
+      const float4 v = reinterpret_cast<const float4*>(p)[i];
+      out[4 * i] = v.x, out[4 * i + 1] = v.y, out[4 * i + 2] = v.z, out[4 * i + 3] = v.w;
+    }
+  } else if constexpr (V == 2) {
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) {
+      const float2 v = reinterpret_cast<const float2*>(p)[i];
+      out[2 * i] = v.x, out[2 * i + 1] = v.y;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = p[i];
+  }
+}
+
+template <int N, int V>
+__device__ __forceinline__ void store_piece(float* __restrict__ p, const float* in) {
+  if constexpr (V == 4) {
+#pragma unroll
+    for (int i = 0; i < N / 4; ++i)
+      reinterpret_cast<float4*>(p)[i] = make_float4(in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3]);
+  } else if constexpr (V == 2) {
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) reinterpret_cast<float2*>(p)[i] = make_float2(in[2 * i], in[2 * i + 1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) p[i] = in[i];
+  }
+}
+
+// vector width of a row piece of P = 2 neighbouring blocks of factor U: 2 U floats starting at a multiple of 2 U
+template <int U, bool VEC>
+constexpr int piece_vec() { return !VEC ? 1 : (U % 2 == 0 ? 4 : 2); }
+
+// the u x u sums of P neighbouring blocks (rows outer, columns inner: the order of poisson_pooled_kernel)
+template <int U, int P>
+__device__ __forceinline__ void pool_blocks(const float (&v)[U][P * U], float* pooled) {
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    float acc = 0.f;
+#pragma unroll
+    for (int dy = 0; dy < U; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < U; ++dx) acc += v[dy][i * U + dx];
+    pooled[i] = acc;
+  }
+}
+
+template <int U, int P, int V>
+__device__ __forceinline__ void replicate_blocks(float* __restrict__ g, int Wp, int y, int x0, const float* gk) {
+  float row[P * U];
+#pragma unroll
+  for (int i = 0; i < P; ++i)
+#pragma unroll
+    for (int dx = 0; dx < U; ++dx) row[i * U + dx] = gk[i];
+#pragma unroll
+  for (int dy = 0; dy < U; ++dy) store_piece<P * U, V>(g + (size_t)(y * U + dy) * Wp + (size_t)x0 * U, row);
+}
+
+template <int U0, int U1, bool VEC>
+__global__ __launch_bounds__(BLOCK) void poisson_mixed_kernel(PoissonMixedArgs a) {
+  __shared__ double smem[BLOCK / 64];
+  constexpr int P = VEC ? 2 : 1;
+  constexpr int V0 = piece_vec<U0, VEC>(), V1 = piece_vec<U1, VEC>();
+  const int y = blockIdx.y;
+  const int x0 = (blockIdx.x * BLOCK + threadIdx.x) * P;
+  double local = 0.0;
+  if (x0 < a.Wd) {  // (VEC: Wd is even, so x0 + 1 < Wd too)
+    const size_t off = (size_t)y * a.Wd + x0;
+    float b[P], c[P], v0[U0][P * U0], v1[U1][P * U1];
+    load_piece<P, VEC ? 2 : 1>(a.background + off, b);
+    load_piece<P, VEC ? 2 : 1>(a.counts + off, c);
+#pragma unroll
+    for (int dy = 0; dy < U0; ++dy)
+      load_piece<P * U0, V0>(a.conv[0] + (size_t)(y * U0 + dy + a.oy[0]) * a.Wp[0] + ((size_t)x0 * U0 + a.ox[0]), v0[dy]);
+#pragma unroll
+    for (int dy = 0; dy < U1; ++dy)
+      load_piece<P * U1, V1>(a.conv[1] + (size_t)(y * U1 + dy + a.oy[1]) * a.Wp[1] + ((size_t)x0 * U1 + a.ox[1]), v1[dy]);
+
+    float p0[P], p1[P], n[P], g[P];
+    pool_blocks<U0, P>(v0, p0);
+    pool_blocks<U1, P>(v1, p1);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      n[i] = fmaxf(p0[i], 0.f);  // clip per component after pooling (npred.py:181-191)
+      n[i] += fmaxf(p1[i], 0.f);
+      n[i] += b[i];              // background added last, un-convolved (npred.py:254-261)
+      float term;
+      poisson_point(n[i], c[i], a.eps, a.inv_n, term, g[i]);
+      local += (double)term;
+    }
+    if (a.npred_out) store_piece<P, VEC ? 2 : 1>(a.npred_out + off, n);
+    if (a.write_grad) {
+      float gk[P];
+#pragma unroll
+      for (int i = 0; i < P; ++i) gk[i] = p0[i] >= 0.f ? g[i] : 0.f;  // clamp backward: passes where pooled >= 0
+      replicate_blocks<U0, P, V0>(a.g[0], a.Wp[0], y, x0, gk);
+#pragma unroll
+      for (int i = 0; i < P; ++i) gk[i] = p1[i] >= 0.f ? g[i] : 0.f;
+      replicate_blocks<U1, P, V1>(a.g[1], a.Wp[1], y, x0, gk);
+    }
+  }
+  const double total = block_sum<BLOCK>(local, smem);
+  if (threadIdx.x == 0) a.partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// any number of components, any factor: one counts pixel per thread, run-time loops over the block
+__global__ __launch_bounds__(BLOCK) void poisson_mixed_generic_kernel(PoissonMixedArgs a) {
+  __shared__ double smem[BLOCK / 64];
+  const int y = blockIdx.y;
+  const int x = blockIdx.x * BLOCK + threadIdx.x;
+  double local = 0.0;
+  if (x < a.Wd) {
+    const size_t off = (size_t)y * a.Wd + x;
+    float pooled[JD_MAX_COMPONENTS];
+    float n = 0.f;
+#pragma unroll
+    for (int k = 0; k < JD_MAX_COMPONENTS; ++k) {
+      if (k >= a.n_comp) break;
+      const int u = a.up[k];
+      float acc = 0.f;
+      for (int dy = 0; dy < u; ++dy) {
+        const float* row = a.conv[k] + (size_t)(y * u + dy + a.oy[k]) * a.Wp[k] + ((size_t)x * u + a.ox[k]);
+        for (int dx = 0; dx < u; ++dx) acc += row[dx];
+      }
+      pooled[k] = acc;
+      n += fmaxf(acc, 0.f);
+    }
+    n += a.background[off];
+    float term, g;
+    poisson_point(n, a.counts[off], a.eps, a.inv_n, term, g);
+    local = (double)term;
+    if (a.npred_out) a.npred_out[off] = n;
+    if (a.write_grad) {
+#pragma unroll
+      for (int k = 0; k < JD_MAX_COMPONENTS; ++k) {
+        if (k >= a.n_comp) break;
+        const int u = a.up[k];
+        const float gk = pooled[k] >= 0.f ? g : 0.f;
+        for (int dy = 0; dy < u; ++dy) {
+          float* row = a.g[k] + (size_t)(y * u + dy) * a.Wp[k] + (size_t)x * u;
+          for (int dx = 0; dx < u; ++dx) row[dx] = gk;
+        }
+      }
+    }
+  }
+  const double total = block_sum<BLOCK>(local, smem);
+  if (threadIdx.x == 0) a.partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+template <int U0, bool VEC>
+static void launch_poisson_mixed_u1(const PoissonMixedArgs& a, dim3 grid, hipStream_t stream) {
+  switch (a.up[1]) {
+    case 1: poisson_mixed_kernel<U0, 1, VEC><<<grid, BLOCK, 0, stream>>>(a); break;
+    case 2: poisson_mixed_kernel<U0, 2, VEC><<<grid, BLOCK, 0, stream>>>(a); break;
+    case 3: poisson_mixed_kernel<U0, 3, VEC><<<grid, BLOCK, 0, stream>>>(a); break;
+    default: poisson_mixed_kernel<U0, 4, VEC><<<grid, BLOCK, 0, stream>>>(a); break;
+  }
+}
+
+template <bool VEC>
+static void launch_poisson_mixed_u0(const PoissonMixedArgs& a, dim3 grid, hipStream_t stream) {
+  switch (a.up[0]) {
+    case 1: launch_poisson_mixed_u1<1, VEC>(a, grid, stream); break;
+    case 2: launch_poisson_mixed_u1<2, VEC>(a, grid, stream); break;
+    case 3: launch_poisson_mixed_u1<3, VEC>(a, grid, stream); break;
+    default: launch_poisson_mixed_u1<4, VEC>(a, grid, stream); break;
+  }
+}
+
+int poisson_mixed_max_partials(int Hd, int Wd) { return ((Wd + BLOCK - 1) / BLOCK) * Hd; }
+
+int launch_poisson_mixed(const PoissonMixedArgs& a, int* n_partials, hipStream_t stream) {
+  const bool two = a.n_comp == 2 && a.up[0] >= 1 && a.up[0] <= 4 && a.up[1] >= 1 && a.up[1] <= 4;
+  auto aligned = [](const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; };
+  // two counts pixels per thread: every row piece then starts at a multiple of its vector width
+  bool vec = two && a.Wd % 2 == 0 && aligned(a.background, 8) && aligned(a.counts, 8) && aligned(a.npred_out, 8);
+  for (int c = 0; vec && c < 2; ++c) {
+    const int v = a.up[c] % 2 == 0 ? 4 : 2;
+    vec = a.Wp[c] % v == 0 && a.ox[c] % v == 0 && aligned(a.conv[c], 4 * v) && (!a.write_grad || aligned(a.g[c], 4 * v));
+  }
+  const int per_block = BLOCK * (vec ? 2 : 1);
+  dim3 grid((a.Wd + per_block - 1) / per_block, a.Hd);
+  *n_partials = grid.x * grid.y;
+  ProfScope prof(JD_KERNEL_POISSON_MIXED, stream);
+  if (!two)
+    poisson_mixed_generic_kernel<<<grid, BLOCK, 0, stream>>>(a);
+  else if (vec)
+    launch_poisson_mixed_u0<true>(a, grid, stream);
+  else
+    launch_poisson_mixed_u0<false>(a, grid, stream);
+  JD_LAUNCH_CHECK();
+  return JD_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // K5: adjoint epilogue. grad[p][q] (+)= coef * scale[p][q] * corr[(p-oy) mod Hp][(q-ox) mod Wp]
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void adjoint_epilogue_kernel(const float* __restrict__ corr,

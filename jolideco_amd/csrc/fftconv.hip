@@ -626,6 +626,68 @@ extern "C" int jd_npred_poisson_fwd_bwd(jd_conv_plan* p, int n_comp, const float
                             Calibration{}, stream);
 }
 
+// Flux components on grids of different up-sampling factors (models/npred.py:279-295: one NPredModel per component with
+// that component's factor; :160-191 sum-pool before the clip; :241-261 the clipped terms are added).  The un-fused
+// stages of npred_poisson_impl with one plan PER COMPONENT: forward into plan c's buffer, one Poisson launch over the
+// counts grid that reads every buffer with its own geometry, adjoint from plan c's gradient buffer.  Components that
+// share a plan object take successive buffer slots of it.
+extern "C" int jd_npred_poisson_mixed_fwd_bwd(jd_conv_plan* const* plans, int n_comp, const float* const* flux,
+                                              const float* const* exposure, const float* const* khat,
+                                              const float* background, const float* counts, float stirling_mean,
+                                              float eps, float* loss_out, float* const* grad_flux, int accumulate,
+                                              float grad_scale, float* npred_out, const int* upsampling, void* stream) {
+  const char* who = "jd_npred_poisson_mixed_fwd_bwd";
+  JD_REQUIRE(plans && flux && exposure && khat && background && counts && loss_out && upsampling, "%s: null argument", who);
+  JD_REQUIRE(n_comp >= 1 && n_comp <= JD_MAX_COMPONENTS, "%s: n_comp = %d not in [1, %d]", who, n_comp, JD_MAX_COMPONENTS);
+  int Hd = 0, Wd = 0, slot[JD_MAX_COMPONENTS] = {0};
+  for (int c = 0; c < n_comp; ++c) {
+    jd_conv_plan* p = plans[c];
+    JD_REQUIRE(p && flux[c] && exposure[c] && khat[c], "%s: plans[%d], flux[%d], exposure[%d] or khat[%d] is null", who, c, c, c, c);
+    if (grad_flux) JD_REQUIRE(grad_flux[c], "%s: grad_flux[%d] is null", who, c);
+    const int u = upsampling[c];
+    JD_REQUIRE(u >= 1 && u <= 8 && p->H % u == 0 && p->W % u == 0,
+               "%s: upsampling[%d] = %d must be in [1, 8] and divide the grid (%d, %d) of plans[%d]", who, c, u, p->H, p->W, c);
+    if (c == 0) Hd = p->H / u, Wd = p->W / u;
+    JD_REQUIRE(p->H == Hd * u && p->W == Wd * u,
+               "%s: shape mismatch: plans[%d] works on (%d, %d), not on upsampling[%d] = %d times the counts grid (%d, %d) "
+               "of component 0", who, c, p->H, p->W, c, u, Hd, Wd);
+    for (int k = 0; k < c; ++k)
+      if (plans[k] == p) ++slot[c];
+  }
+  jd_conv_plan* p0 = plans[0];
+  JD_REQUIRE(poisson_mixed_max_partials(Hd, Wd) <= p0->partials_cap, "%s: partial sums of a (%d, %d) counts grid do not fit plans[0]",
+             who, Hd, Wd);
+  hipStream_t s = as_stream(stream);
+  int rc = JD_OK;
+  for (int c = 0; c < n_comp; ++c)
+    if ((rc = ensure_component_buffers(plans[c], slot[c] + 1))) return rc;
+
+  // forward model per component on its own grid (models/npred.py:175-179)
+  for (int c = 0; c < n_comp; ++c)
+    if ((rc = conv_forward(plans[c], slot[c], flux[c], exposure[c], khat[c], s))) return rc;
+
+  // sum-pool + clip per component + background + NLL + replicated gradient (models/npred.py:181-191,254-261; loss.py:35-37)
+  PoissonMixedArgs a{};
+  for (int c = 0; c < n_comp; ++c) {
+    const jd_conv_plan* p = plans[c];
+    a.conv[c] = p->conv[slot[c]], a.g[c] = p->pad[slot[c]];
+    a.up[c] = upsampling[c], a.Wp[c] = p->Wp, a.oy[c] = p->py, a.ox[c] = p->px;
+  }
+  const double n_pix = (double)Hd * (double)Wd;
+  a.background = background, a.counts = counts, a.npred_out = npred_out, a.partials = p0->partials;
+  a.n_comp = n_comp, a.Hd = Hd, a.Wd = Wd, a.eps = eps, a.inv_n = (float)(1.0 / n_pix);
+  a.write_grad = grad_flux ? 1 : 0;
+  int n_partials = 0;
+  if ((rc = launch_poisson_mixed(a, &n_partials, s))) return rc;
+  if ((rc = launch_finalize_sum(p0->partials, n_partials, 1.0 / n_pix, (double)stirling_mean, loss_out, 0, s))) return rc;
+  if (!grad_flux) return JD_OK;
+
+  // adjoint per component: d loss / d flux_c = E_c * corr(psf_c, g_c)
+  for (int c = 0; c < n_comp; ++c)
+    if ((rc = corr_backward_into(plans[c], slot[c], khat[c], exposure[c], grad_flux[c], grad_scale, accumulate, s))) return rc;
+  return JD_OK;
+}
+
 extern "C" int jd_npred_poisson_batch_multi_fwd_bwd(jd_conv_plan* p, int n_datasets, int n_comp, const float* const* flux,
                                                     const float* const* exposure, const float* const* khat,
                                                     const float* const* background, const float* const* counts,

@@ -22,6 +22,24 @@ struct PoissonArgs {
   double* partials_b;
 };
 
+// The Poisson pass of ONE dataset whose flux components live on grids of DIFFERENT up-sampling factors
+// (jd_npred_poisson_mixed_fwd_bwd): component c's convolution is read from its own plan's buffer with that plan's row
+// pitch, crop offset and factor, and its masked, up[c] x up[c]-replicated gradient goes to that plan's adjoint input.
+struct PoissonMixedArgs {
+  const float* conv[JD_MAX_COMPONENTS];  // (Hd * up[c] + ..., Wp[c]) convolution of component c, read at (oy[c], ox[c])
+  float* g[JD_MAX_COMPONENTS];           // row pitch Wp[c]: masked d loss / d conv_c on rows / columns [0, Hd * up[c]) x [0, Wd * up[c])
+  int up[JD_MAX_COMPONENTS], Wp[JD_MAX_COMPONENTS], oy[JD_MAX_COMPONENTS], ox[JD_MAX_COMPONENTS];
+  const float* background;
+  const float* counts;
+  float* npred_out;  // nullable
+  double* partials;
+  int n_comp, Hd, Wd;  // (Hd, Wd): the counts grid
+  float eps, inv_n;
+  int write_grad;
+};
+int launch_poisson_mixed(const PoissonMixedArgs& a, int* n_partials, hipStream_t stream);
+int poisson_mixed_max_partials(int Hd, int Wd);
+
 int launch_pad_mul(const float* image, const float* scale, float* padded, int H, int W, int Hp, int Wp,
                    hipStream_t stream);
 int launch_cmul(float2* spec, const float2* khat, size_t n, bool conj, hipStream_t stream);

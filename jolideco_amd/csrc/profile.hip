@@ -157,6 +157,7 @@ extern "C" const char* jd_kernel_name(int kernel) {
     case JD_KERNEL_GMM_EXACT: return "gmm_exact_kernel";
     case JD_KERNEL_GMM_STAGE: return "gmm_stage_kernel";
     case JD_KERNEL_SHIFT: return "shift_kernels";
+    case JD_KERNEL_POISSON_MIXED: return "poisson_mixed_kernel";
     default: return "?";
   }
 }

@@ -372,7 +372,7 @@ class NPredModels(nn.ModuleDict):
         psfs = dataset_psfs(dataset, components)
         factors = {c.upsampling_factor or 1 for c in components.values()}
         if len(factors) != 1:
-            raise NotImplementedError("all components of a fit must share one upsampling_factor in jolideco_amd")
+            return cls._from_dataset_mixed_factors(dataset, components, psfs, calibration, device)
         own = (max(p.shape[0] for p in psfs.values()), max(p.shape[1] for p in psfs.values()))
         kernel_shape = own if kernel_shape is None else (max(own[0], kernel_shape[0]), max(own[1], kernel_shape[1]))
         psf_scale = None if calibration is None else float(calibration.psf_scale.detach().cpu())
@@ -393,6 +393,35 @@ class NPredModels(nn.ModuleDict):
         models = cls(background, calibration, values)
         models.shared_operator = cls._components_share_the_operator(psfs, values, calibration)
         return models
+
+    @classmethod
+    def _from_dataset_mixed_factors(cls, dataset, components, psfs, calibration, device):
+        """Components with DIFFERENT up-sampling factors (models/npred.py:279-295: one NPredModel per component with that
+        component's factor): every component gets its own plan on its own grid, with its PSF as given (no embedding in
+        a common kernel shape -- the plans differ anyway) and its own convolution method; the step runs through
+        jd_npred_poisson_mixed_fwd_bwd (`fwd_bwd`)."""
+        if calibration is not None:
+            raise NotImplementedError(
+                "a dataset calibration together with flux components of different upsampling_factor is not implemented "
+                "in jolideco_amd (give all components one factor, or drop the calibration)"
+            )
+        values = [
+            (name, NPredModel.from_numpy(exposure=dataset["exposure"], psf=psfs[name],
+                                         upsampling_factor=component.upsampling_factor, device=device))
+            for name, component in components.items()
+        ]
+        background = _to_device_image(dataset["background"], device)[None, None]
+        models = cls(background, None, values)
+        models.shared_operator = False
+        return models
+
+    @property
+    def mixed_upsampling(self):
+        """True when the components of this dataset live on grids of different up-sampling factors."""
+        mixed = self.__dict__.get("_mixed_upsampling")
+        if mixed is None:
+            mixed = self.__dict__["_mixed_upsampling"] = len({m.upsampling_factor or 1 for m in self.values()}) > 1
+        return mixed
 
     # Several components, ONE operator.  The reference builds every component's model of a dataset from the same exposure
     # and, unless `psf` is a dict by component, the same PSF (models/npred.py:279-295), and adds the clipped convolutions
@@ -464,6 +493,16 @@ class NPredModels(nn.ModuleDict):
         """One fused C-ABI call: forward model + Poisson NLL (+ d loss / d flux_c).  ``flux_nonneg``: the caller
         guarantees flux >= 0; components that share the operator (`shared_operator`) are then evaluated as their sum."""
         models = list(self.values())
+        if self.mixed_upsampling:
+            # one plan and one factor per component (jd_npred_poisson_mixed_fwd_bwd); never reached by fits whose
+            # components share one factor
+            ConvPlan.npred_poisson_mixed_fwd_bwd(
+                plans=[m.plan for m in models], upsamplings=[m.upsampling_factor or 1 for m in models],
+                fluxes=list(fluxes), exposures=[m.exposure for m in models], khats=[m.khat for m in models],
+                background=self.background, counts=counts, stirling=stirling, loss_out=loss_out, grads=grads,
+                accumulate=accumulate, grad_scale=grad_scale, npred_out=npred_out,
+            )
+            return
         if (flux_nonneg and self.shared_operator and len(models) > 1 and not accumulate and npred_out is None
                 and os.environ.get("JOLIDECO_MERGE_COMPONENTS", "1") != "0"):
             from ..ops import copy_image_to, sum_images

@@ -237,6 +237,31 @@ class ConvPlan:
             )
         )
 
+    @staticmethod
+    def npred_poisson_mixed_fwd_bwd(
+        plans, upsamplings, fluxes, exposures, khats, background, counts, stirling, loss_out, grads=None,
+        accumulate=False, grad_scale=1.0, npred_out=None, eps=POISSON_EPS,
+    ):
+        """Fused forward model + Poisson NLL (+ gradient) of one dataset whose flux components live on grids of
+        different up-sampling factors: ``plans[c]`` / ``upsamplings[c]`` are the plan and the factor of component c
+        (jd_npred_poisson_mixed_fwd_bwd, include/jolideco_hip.h)."""
+        n = len(plans)
+        if not (len(upsamplings) == len(fluxes) == len(exposures) == len(khats) == n):
+            raise ValueError("plans, upsamplings, fluxes, exposures and khats must have the same length")
+        if grads is not None and len(grads) != n:
+            raise ValueError("one gradient image per flux component")
+        for plan, f in zip(plans, fluxes):
+            plan._check_image(f, "flux")
+        handles = (c_void_p * n)(*[plan._handle.value for plan in plans])
+        factors = (c_int * n)(*[int(u) for u in upsamplings])
+        check(
+            _hip.lib().jd_npred_poisson_mixed_fwd_bwd(
+                handles, n, ptr_array(fluxes), ptr_array(exposures), ptr_array(khats), ptr(background), ptr(counts),
+                c_float(stirling), c_float(eps), ptr(loss_out), ptr_array(grads) if grads is not None else None,
+                int(accumulate), c_float(grad_scale), ptr(npred_out), factors, stream_ptr(background.device),
+            )
+        )
+
     MAX_BATCH = 16  # SEP_MAX_BATCH of csrc/kernels.h
     MAX_BATCH_COMPONENTS = 4  # SEP_BATCH_MAX_COMP
 
