@@ -278,6 +278,28 @@ int jd_gmm_destroy(jd_gmm* gmm);
  * MFMAs per component and 16 patches, bit-identical results); 0 = dense variant. */
 int jd_gmm_is_triangular(const jd_gmm* gmm);
 
+/* IMAGE NORM of the prior (jolideco/utils/norms.py:225-426; priors/patches/core.py:190 `normed = self.norm(flux)`): the
+ * three jd_gmm_prior_* calls below evaluate the mixture on n(flux) and return the gradient with respect to the RAW flux.
+ *   kind 0 identity   n = f                              (p0, p1 unused; the state of a new handle)
+ *        1 asinh      n = asinh(f / p0) / asinh(p1 / p0)             (p0 = alpha, p1 = beta)
+ *        2 fixed-max  n = clip(f / p0, 0, 1)                         (p0 = max_value)
+ *        3 sigmoid    n = 1 / (1 + exp(-(f - p1 / 2) / p0))          (p0 = alpha, p1 = beta)
+ *        4 atan       n = 2 atan(f / p0) / pi                        (p0 = alpha)
+ *        5 log        n = log(f / p0)                                (p0 = alpha)
+ *        6 power      n = (f / p1)^p0                                (p0 = alpha, p1 = beta)
+ * Phase 1 of a pass with kind != 0 first writes n(flux) into an (H, W) image of the handle (one streaming kernel) and
+ * every later kernel of the phase reads that image -- the `> -1e5` patch filter acts on normed values, as in the
+ * reference; phase 2 multiplies every pixel's overlap-add by n'(raw flux of the pixel), (grad_coef * sum) * n', in all
+ * three output forms (accumulate, band, optimizer step); a pixel whose sum is exactly 0 receives nothing (never 0 * inf).
+ * The norm is a state of the HANDLE, taken by the next jd_gmm_prior_* call: callers that share a handle between priors
+ * set it in front of every call.  A phase-2 call must find the norm of its phase 1 (JD_ERR_INVALID otherwise).
+ * The parameters are constants (the reference trains them unless frozen). */
+typedef struct {
+  int kind;
+  float p0, p1;
+} jd_image_norm;
+int jd_gmm_set_image_norm(jd_gmm* gmm, const jd_image_norm* norm);
+
 /* log-prior value and gradient of GMMPatchPrior.__call__ (priors/patches/core.py:189-246) with
  * IdentityImageNorm, SubtractMeanPatchNorm (utils/norms.py:97-103), cycle-spin roll by
  * (shift_y, shift_x) (utils/torch.py:108-119), patch size 8, stride `stride`

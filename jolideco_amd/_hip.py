@@ -77,6 +77,7 @@ EXPORTS = {
     "jd_gmm_create": (c_int, [c_int, c_int, fp, fp, fp, fp, POINTER(c_void_p)]),
     "jd_gmm_destroy": (c_int, [c_void_p]),
     "jd_gmm_is_triangular": (c_int, [c_void_p]),
+    "jd_gmm_set_image_norm": (c_int, [c_void_p, c_void_p]),
     "jd_gmm_prior_fwd_bwd": (
         c_int,
         [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int,
@@ -137,6 +138,12 @@ class Step(ctypes.Structure):
         ("one_minus_beta2", c_float), ("bias2_sqrt", c_float), ("eps", c_float), ("lr", c_float),
         ("use_log_flux", c_int), ("sgd", c_int), ("bias_dev", c_void_p),
     ]
+
+
+class ImageNormStruct(ctypes.Structure):
+    """`jd_image_norm` of include/jolideco_hip.h: kind and parameters of the prior's image norm."""
+
+    _fields_ = [("kind", c_int), ("p0", c_float), ("p1", c_float)]
 
 
 KERNEL_IDS = {

@@ -2091,6 +2091,97 @@ __global__ __launch_bounds__(256) void gmm_lse_finalize_kernel(const double* par
   }
 }
 
+// ---- image norm of the prior (jolideco/utils/norms.py:225-426; jd_image_norm of the header) ------------------------
+// n(f) is written once per pass into an image of the handle (gmm_image_norm_kernel: everything in phase 1 reads it in
+// place of the flux); n'(f) is evaluated by the gather from the pixel's RAW flux (chain rule of the overlap-add).
+enum { NORM_IDENTITY = 0, NORM_ASINH = 1, NORM_FIXED_MAX = 2, NORM_SIGMOID = 3, NORM_ATAN = 4, NORM_LOG = 5, NORM_POWER = 6,
+       NORM_COUNT = 7 };
+constexpr float NORM_PI = 3.14159265358979323846f;  // float(torch.pi)
+
+struct ImageNormArgs {
+  int kind;
+  float p0, p1;
+  float c;  // asinh: asinh(p1 / p0), the denominator (host, jd_gmm_set_image_norm); otherwise unused
+};
+
+template <int KIND>
+__device__ __forceinline__ float image_norm_value(float f, const ImageNormArgs& nm) {
+#pragma clang fp contract(off)
+  if (KIND == NORM_ASINH) return asinhf(f / nm.p0) / nm.c;
+  if (KIND == NORM_FIXED_MAX) {
+    const float t = f / nm.p0;
+    return t < 0.f ? 0.f : (t > 1.f ? 1.f : t);  // (torch.clip: a NaN stays a NaN)
+  }
+  if (KIND == NORM_SIGMOID) return 1.f / (1.f + expf(-(f - nm.p1 / 2.f) / nm.p0));
+  if (KIND == NORM_ATAN) return 2.f * atanf(f / nm.p0) / NORM_PI;
+  if (KIND == NORM_LOG) return logf(f / nm.p0);
+  if (KIND == NORM_POWER) return powf(f / nm.p1, nm.p0);
+  return f;
+}
+
+// n'(f); the kind is uniform over the launch (one scalar branch per call)
+__device__ __forceinline__ float image_norm_deriv(float f, const ImageNormArgs& nm) {
+#pragma clang fp contract(off)  // (the same bits wherever it is inlined: tiled = per-pixel gather)
+  switch (nm.kind) {
+    case NORM_ASINH: {
+      const float t = f / nm.p0;
+      return 1.f / (nm.p0 * sqrtf(1.f + t * t) * nm.c);
+    }
+    case NORM_FIXED_MAX: {
+      const float t = f / nm.p0;
+      return t >= 0.f && t <= 1.f ? 1.f / nm.p0 : 0.f;  // (inclusive ends: torch.clip's backward)
+    }
+    case NORM_SIGMOID: {
+      const float sg = 1.f / (1.f + expf(-(f - nm.p1 / 2.f) / nm.p0));
+      return sg * (1.f - sg) / nm.p0;
+    }
+    case NORM_ATAN: {
+      const float t = f / nm.p0;
+      return 2.f / (NORM_PI * nm.p0 * (1.f + t * t));
+    }
+    case NORM_LOG: return 1.f / f;
+    case NORM_POWER: return (nm.p0 / nm.p1) * powf(f / nm.p1, nm.p0 - 1.f);
+    default: return 1.f;
+  }
+}
+
+// out[i] = n(in[i]), i < n: a streaming pass (4 bytes read + 4 written per pixel), grid-stride; instantiated per kind (no
+// branch in the pixel loop).  The first 4 n4 pixels go in 16-byte loads and stores (n4 = n / 4 where both images are
+// 16-byte aligned, else 0), the rest -- the up to 3 pixels of the tail, or everything -- pixel by pixel.
+template <int KIND>
+__global__ __launch_bounds__(256) void gmm_image_norm_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n,
+                                                             ImageNormArgs nm, size_t n4) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nthreads = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < n4; i += nthreads) {
+    const float4 v = reinterpret_cast<const float4*>(in)[i];
+    reinterpret_cast<float4*>(out)[i] = make_float4(image_norm_value<KIND>(v.x, nm), image_norm_value<KIND>(v.y, nm),
+                                                    image_norm_value<KIND>(v.z, nm), image_norm_value<KIND>(v.w, nm));
+  }
+  for (size_t i = 4 * n4 + tid; i < n; i += nthreads) out[i] = image_norm_value<KIND>(in[i], nm);
+}
+
+static int launch_image_norm(const float* in, float* out, size_t n, const ImageNormArgs& nm, int n_cu, hipStream_t s) {
+  const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const size_t n4 = aligned ? n / 4 : 0;
+  const size_t items = n4 + (n - 4 * n4);
+  size_t blocks = (items + 255) / 256;
+  const size_t cap = (size_t)n_cu * 8;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  const unsigned gb = (unsigned)blocks;
+  switch (nm.kind) {
+    case NORM_ASINH: gmm_image_norm_kernel<NORM_ASINH><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
+    case NORM_FIXED_MAX: gmm_image_norm_kernel<NORM_FIXED_MAX><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
+    case NORM_SIGMOID: gmm_image_norm_kernel<NORM_SIGMOID><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
+    case NORM_ATAN: gmm_image_norm_kernel<NORM_ATAN><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
+    case NORM_LOG: gmm_image_norm_kernel<NORM_LOG><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
+    case NORM_POWER: gmm_image_norm_kernel<NORM_POWER><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
+    default: JD_REQUIRE(false, "image norm kind %d has no kernel", nm.kind);
+  }
+  JD_LAUNCH_CHECK();
+  return JD_OK;
+}
+
 struct GmmGatherArgs {
   const float* gpatch;
   float* grad;
@@ -2116,8 +2207,22 @@ struct GmmGatherArgs {
   int do_step;
   int preload;  // do_step: the step's streams are loaded before the patch rows (JD_GMM_GATHER_PRELOAD=0: behind the barrier)
   AdamArgs step;
+  // image norm of the pass (kind != 0: the NORM instantiations of the gather kernels): every pixel's coef * sum is
+  // multiplied by n'(raw_flux[pixel]), the rounded product (coef * sum) * n' in all three output forms; a pixel whose sum
+  // is exactly 0 receives nothing (n' may be infinite there: log norm of a zero pixel)
+  ImageNormArgs norm;
+  const float* raw_flux;
 };
 
+// (coef * sum) * n'(f), each product rounded (callers run under `fp contract(off)`); nothing for an exact zero sum
+__device__ __forceinline__ float gather_normed_term(const GmmGatherArgs& a, float sum, float f) {
+#pragma clang fp contract(off)
+  if (sum == 0.f) return 0.f;
+  const float cs = a.coef * sum;
+  return cs * image_norm_deriv(f, a.norm);
+}
+
+template <bool NORM>
 __global__ __launch_bounds__(256) void gmm_gather_kernel(GmmGatherArgs a) {
 #pragma clang fp contract(off)
   use_device_shift(a);
@@ -2151,6 +2256,15 @@ __global__ __launch_bounds__(256) void gmm_gather_kernel(GmmGatherArgs a) {
       any = true;
     }
   }
+  if (NORM) {  // the same three forms with the chain rule of the image norm
+    const int yy = wrap(Y - a.shift_y, a.H), xx = wrap(X - a.shift_x, a.W);
+    const size_t idx = (size_t)yy * a.W + xx;
+    const bool live = any && sum != 0.f;
+    const float term = live ? gather_normed_term(a, sum, a.raw_flux[idx]) : 0.f;
+    if (a.band) a.band[(size_t)(Y - a.y_begin) * a.W + X] = term;
+    else if (live) a.grad[idx] += term;
+    return;
+  }
   if (a.band) {
     a.band[(size_t)(Y - a.y_begin) * a.W + X] = any ? a.coef * sum : 0.f;
     return;
@@ -2177,6 +2291,7 @@ __global__ __launch_bounds__(256) void gmm_gather_kernel(GmmGatherArgs a) {
 // floor(38 / s) + 1 = 8, 7, 6.  Columns: the tile's first column is shift_x (mod 4), not aligned with the grid: 10.
 constexpr int GATHER_T = 32, GATHER_MAX_P = JD_GATHER_MAX_P, GATHER_MAX_PX = JD_GATHER_MAX_P + 1;
 
+template <bool NORM>
 __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
 #pragma clang fp contract(off)
   use_device_shift(a);
@@ -2211,6 +2326,7 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
   const int Yt = Y0 + (tid >> 3), Xt = X0 + (tid & 7) * 4;
   const bool pre = a.do_step && a.vec && Yt < a.y_end && Xt >= 0 && Xt + 3 < a.W;
   const bool early = pre && a.preload;
+  bool loaded = early;  // the step's streams of this thread are in its registers
   float4 pre_g = make_float4(0.f, 0.f, 0.f, 0.f), pre_t = pre_g, pre_f = pre_g, pre_m = pre_g, pre_v = pre_g;
   float4 pre_k = make_float4(1.f, 1.f, 1.f, 1.f);
   auto load_step_streams = [&]() {
@@ -2280,19 +2396,45 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
       }
     }
   }
+  const size_t row = (size_t)yy * a.W;
+  // image norm: term[i] = (coef * sum[i]) * n'(raw flux of the pixel) replaces coef * sum[i] below; a pixel without a
+  // patch or with an exactly zero sum is not `any` any more (it receives nothing, n' is not evaluated)
+  float term[4] = {0.f, 0.f, 0.f, 0.f};
+  if (NORM) {
+    const bool group = a.vec && Xg >= 0 && Xg + 3 < a.W;
+    float fr[4] = {0.f, 0.f, 0.f, 0.f};
+    if (group && a.do_step && a.raw_flux == a.step.flux_in) {
+      if (!loaded) load_step_streams(), loaded = true;  // (JD_GMM_GATHER_PRELOAD=0: now, once, not here AND below)
+      fr[0] = pre_f.x, fr[1] = pre_f.y, fr[2] = pre_f.z, fr[3] = pre_f.w;  // (the step's own flux stream, already here)
+    } else if (group) {
+      const float4 f4 = *reinterpret_cast<const float4*>(a.raw_flux + row + wrap(Xg - a.shift_x, a.W));
+      fr[0] = f4.x, fr[1] = f4.y, fr[2] = f4.z, fr[3] = f4.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (Xg + i >= 0 && Xg + i < a.W) fr[i] = a.raw_flux[row + wrap(Xg + i - a.shift_x, a.W)];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      any[i] = any[i] && sum[i] != 0.f;
+      if (any[i]) term[i] = gather_normed_term(a, sum[i], fr[i]);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) term[i] = a.coef * sum[i];
+  }
   if (a.band) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      if (Xg + i >= 0 && Xg + i < a.W) a.band[(size_t)(Y - a.y_begin) * a.W + Xg + i] = any[i] ? a.coef * sum[i] : 0.f;
+      if (Xg + i >= 0 && Xg + i < a.W) a.band[(size_t)(Y - a.y_begin) * a.W + Xg + i] = any[i] ? term[i] : 0.f;
     return;
   }
-  const size_t row = (size_t)yy * a.W;
   if (a.vec && Xg >= 0 && Xg + 3 < a.W) {
     // the un-rolled column of the group is a multiple of 4 and the group does not wrap (W % 4 == 0)
     const size_t idx = row + wrap(Xg - a.shift_x, a.W);
     if (a.do_step) {
       const AdamArgs& st = a.step;  // (`pre` holds here: the loads were issued at the top of the kernel)
-      if (!early) load_step_streams();  // (JD_GMM_GATHER_PRELOAD=0: behind the barrier, as before)
+      if (!loaded) load_step_streams();  // (JD_GMM_GATHER_PRELOAD=0: behind the barrier, as before)
       const float4 g4 = pre_g, t4 = pre_t, f4 = pre_f, m4 = pre_m, v4 = pre_v, k4 = pre_k;
       float g[4] = {g4.x, g4.y, g4.z, g4.w};
       float th[4] = {t4.x, t4.y, t4.z, t4.w}, f[4] = {f4.x, f4.y, f4.z, f4.w};
@@ -2300,7 +2442,7 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
       float mk[4] = {k4.x, k4.y, k4.z, k4.w};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if (any[i]) g[i] += a.coef * sum[i];
+        if (any[i]) g[i] += term[i];
         adam_pixel(th[i], f[i], m[i], v[i], g[i], mk[i], st);
       }
       *reinterpret_cast<float4*>(st.theta + idx) = make_float4(th[0], th[1], th[2], th[3]);
@@ -2311,10 +2453,10 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
       }
     } else if (any[0] || any[1] || any[2] || any[3]) {
       float4 g4 = *reinterpret_cast<const float4*>(a.grad + idx);
-      if (any[0]) g4.x += a.coef * sum[0];
-      if (any[1]) g4.y += a.coef * sum[1];
-      if (any[2]) g4.z += a.coef * sum[2];
-      if (any[3]) g4.w += a.coef * sum[3];
+      if (any[0]) g4.x += term[0];
+      if (any[1]) g4.y += term[1];
+      if (any[2]) g4.z += term[2];
+      if (any[3]) g4.w += term[3];
       *reinterpret_cast<float4*>(a.grad + idx) = g4;
     }
     return;
@@ -2327,14 +2469,14 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
     if (a.do_step) {
       const AdamArgs& st = a.step;
       float g = st.grad_flux[idx];
-      if (any[i]) g += a.coef * sum[i];
+      if (any[i]) g += term[i];
       float th = st.theta[idx], f = st.flux_in[idx], m = st.sgd ? 0.f : st.m[idx], v = st.sgd ? 0.f : st.v[idx];
       const float mk = st.mask ? st.mask[idx] : 1.f;
       adam_pixel(th, f, m, v, g, mk, st);
       st.theta[idx] = th, st.flux_out[idx] = f;
       if (!st.sgd) st.m[idx] = m, st.v[idx] = v;
     } else if (any[i]) {
-      a.grad[idx] += a.coef * sum[i];
+      a.grad[idx] += term[i];
     }
   }
 }
@@ -2465,10 +2607,14 @@ struct GmmPass {  // a pass between its two phases (gmm_prior_impl): what the ga
   bool fused = false, lse_screened = false;
   int gen = 0;
   const int* shift_dev = nullptr;
+  jd::ImageNormArgs norm{};  // image norm of its phase 1 (the gather's chain rule must be that norm's)
 };
 
 struct jd_gmm {
   GmmPass pass;
+  jd::ImageNormArgs norm{};  // image norm the next prior call takes (jd_gmm_set_image_norm; kind 0 = identity)
+  float* normed = nullptr;   // n(flux) of the pass, (H, W): what phase 1 reads in place of the flux
+  size_t normed_cap = 0;
   unsigned long long* clock_stamps = nullptr;  // jd_gmm_screen_clock: 2 x SCREEN_CLOCK_CAP ticks, zero = not written
   int K = 0;
   bool triangular = true;  // every P_k upper triangular -> zero blocks are skipped
@@ -2734,6 +2880,7 @@ extern "C" int jd_gmm_destroy(jd_gmm* g) {
   if (!g) return JD_OK;
   (void)hipDeviceSynchronize();
   if (g->clock_stamps) (void)hipFree(g->clock_stamps);
+  if (g->normed) (void)hipFree(g->normed);
   for (float* p : {g->afrag, g->mfrag, g->const_k, g->gfrag, g->gpatch, g->vpatch})
     if (p) (void)hipFree(p);
   if (g->argmax) (void)hipFree(g->argmax);
@@ -3107,6 +3254,27 @@ static int screened_forward(jd_gmm* g, const GmmFwdArgs& a, hipStream_t s, int* 
   return JD_OK;
 }
 
+// The image norm the following jd_gmm_prior_* calls of this handle apply (header: jd_image_norm).
+extern "C" int jd_gmm_set_image_norm(jd_gmm* g, const jd_image_norm* norm) {
+  JD_REQUIRE(norm, "jd_gmm_set_image_norm: null argument");
+  JD_REQUIRE(norm->kind >= 0 && norm->kind < NORM_COUNT, "jd_gmm_set_image_norm: unknown image norm kind %d", norm->kind);
+  if (norm->kind != NORM_IDENTITY) {
+    // every norm divides by a scale (asinh, sigmoid, atan, log: alpha = p0; fixed-max: max_value = p0; power: beta = p1)
+    const float scale = norm->kind == NORM_POWER ? norm->p1 : norm->p0;
+    JD_REQUIRE(std::isfinite(norm->p0) && std::isfinite(norm->p1), "jd_gmm_set_image_norm: non-finite parameter (%g, %g) of image norm kind %d",
+               (double)norm->p0, (double)norm->p1, norm->kind);
+    JD_REQUIRE(scale != 0.f, "jd_gmm_set_image_norm: image norm kind %d divides by its scale parameter, which is 0", norm->kind);
+    JD_REQUIRE(norm->kind != NORM_ASINH || norm->p1 != 0.f, "jd_gmm_set_image_norm: asinh norm with beta = 0 (asinh(beta / alpha) = 0 divides)");
+  }
+  JD_REQUIRE(g, "jd_gmm_set_image_norm: null argument");
+  ImageNormArgs nm{};
+  nm.kind = norm->kind;
+  if (nm.kind != NORM_IDENTITY) nm.p0 = norm->p0, nm.p1 = norm->p1;
+  if (nm.kind == NORM_ASINH) nm.c = std::asinh(nm.p1 / nm.p0);
+  g->norm = nm;
+  return JD_OK;
+}
+
 static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride, int shift_y,
                           int shift_x, int patch_row_begin, int patch_row_end, int marginalize,
                           float value_scale, float* value_out, int accumulate_value, float grad_coef,
@@ -3142,7 +3310,15 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
   // the two halves may sit on different streams: the caller runs the first beside the likelihood launches of the step (it
   // does not touch the gradient image) and joins the streams in front of the second (jolideco_amd/core.py).
   bool screened = false, fused = false, lse_screened = false;
+  const ImageNormArgs norm = g->norm;
+  const bool has_norm = norm.kind != NORM_IDENTITY;
+  const float* const raw_flux = flux;
   if (phases & 1) {
+    if (has_norm) {  // everything below reads n(flux); it still only READS the flux (legal beside the likelihood)
+      if ((rc = grow(&g->normed, &g->normed_cap, (size_t)H * W))) return rc;
+      if ((rc = launch_image_norm(raw_flux, g->normed, (size_t)H * W, norm, g->n_cu, s))) return rc;
+      flux = g->normed;
+    }
     if ((rc = grow(&g->partials, &g->partials_cap, (size_t)((n + 31) / 32 + 4)))) return rc;
     // option JD_GMM_SCREEN = 0 forces the dense fp32 kernel (testing / tuning)
     screened = !marginalize && g->screen_ok && opt_value(OPT_GMM_SCREEN, 1) != 0 && !opt_is_set(OPT_GMM_DENSE);
@@ -3250,13 +3426,14 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
     JD_LAUNCH_CHECK();
     }
 
-    g->pass = GmmPass{true, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, fused, lse_screened, g->gen, shift_dev};
+    g->pass = GmmPass{true, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, fused, lse_screened, g->gen, shift_dev, norm};
     if (!(phases & 2)) return JD_OK;
   } else {
     const GmmPass& ps = g->pass;
     JD_REQUIRE(ps.valid && ps.H == H && ps.W == W && ps.stride == stride && ps.shift_y == shift_y && ps.shift_x == shift_x &&
                    ps.row_begin == patch_row_begin && ps.row_end == patch_row_end && ps.marginalize == marginalize &&
-                   ps.gen == g->gen && ps.shift_dev == shift_dev && grad_flux_accum,
+                   ps.gen == g->gen && ps.shift_dev == shift_dev && grad_flux_accum && ps.norm.kind == norm.kind &&
+                   ps.norm.p0 == norm.p0 && ps.norm.p1 == norm.p1,
                "jd_gmm_prior_fwd_bwd: phase 2 (gather) without the matching phase 1 of the same pass");
     fused = ps.fused, lse_screened = ps.lse_screened;
   }
@@ -3268,10 +3445,11 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
   ga.y_end = (patch_row_end - 1) * stride + P;
   ga.coef = grad_coef;
   ga.band = band_out;
+  ga.norm = norm, ga.raw_flux = raw_flux;
   if (fused) ga.winner = g->winner, ga.grec = g->grec, ga.flag = g->screen_ctl, ga.gen = g->gen;
   {
     auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
-    ga.vec = W % 4 == 0 && aligned(grad_flux_accum) ? 1 : 0;
+    ga.vec = W % 4 == 0 && aligned(grad_flux_accum) && (!has_norm || aligned(raw_flux)) ? 1 : 0;
     if (step) {
       ga.do_step = 1, ga.step = *step, ga.y_begin = 0, ga.y_end = H;  // every pixel of the image takes the step
       ga.preload = opt_value(OPT_GMM_GATHER_PRELOAD, 1) != 0;
@@ -3283,10 +3461,12 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
     if (stride >= 4 && opt_value(OPT_GMM_GATHER_TILED, 1) != 0) {
       // (x: the first tile starts up to 3 pixels left of the image so that the pixel groups are aligned un-rolled)
       dim3 grid((W + 3 + GATHER_T - 1) / GATHER_T, (ga.y_end - ga.y_begin + GATHER_T - 1) / GATHER_T);
-      gmm_gather_tile_kernel<<<grid, 256, 0, s>>>(ga);
+      if (has_norm) gmm_gather_tile_kernel<true><<<grid, 256, 0, s>>>(ga);
+      else gmm_gather_tile_kernel<false><<<grid, 256, 0, s>>>(ga);
     } else {
       dim3 grid((W + 255) / 256, ga.y_end - ga.y_begin);
-      gmm_gather_kernel<<<grid, 256, 0, s>>>(ga);
+      if (has_norm) gmm_gather_kernel<true><<<grid, 256, 0, s>>>(ga);
+      else gmm_gather_kernel<false><<<grid, 256, 0, s>>>(ga);
     }
   }
   JD_LAUNCH_CHECK();

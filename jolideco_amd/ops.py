@@ -380,11 +380,24 @@ class GmmHandle:
         except Exception:
             pass
 
+    def set_image_norm(self, norm):
+        """Hand the image norm of the NEXT prior call to the library (jd_gmm_set_image_norm).  Priors with different norms
+        may share this handle (`GaussianMixtureModel.handle` caches one per device), so every prior call sets it anew;
+        ``norm``: an `ImageNorm` with a device kind, or None = identity."""
+        kind, p0, p1 = (0, 0.0, 0.0) if norm is None else norm.device_params()
+        if kind is None:
+            raise NotImplementedError(f"image norm {type(norm).__name__} has no HIP kernel")
+        data = _hip.ImageNormStruct(int(kind), float(p0), float(p1))
+        check(_hip.lib().jd_gmm_set_image_norm(self._handle, ctypes.byref(data)))
+
     def prior_fwd_bwd(self, flux, stride, shifts, value_out, value_scale, grad=None, grad_coef=0.0,
-                      marginalize=False, patch_rows=(0, -1), accumulate_value=False, argmax_out=None, band_out=None, phases=3):
+                      marginalize=False, patch_rows=(0, -1), accumulate_value=False, argmax_out=None, band_out=None, phases=3,
+                      norm=None):
         """``band_out``: instead of accumulating into ``grad``, write the gradient of the patch rows ``patch_rows`` as the
-        band of the rolled frame they cover (jd_gmm_prior_band_fwd_bwd; `band_rows` gives its extent)."""
+        band of the rolled frame they cover (jd_gmm_prior_band_fwd_bwd; `band_rows` gives its extent).
+        ``norm``: the prior's image norm (None = identity); the gradient is the one with respect to the raw flux."""
         flux = require_hip_tensor(flux, "flux")
+        self.set_image_norm(norm)
         H, W = flux.shape[-2:]
         if flux.numel() != H * W:
             raise ValueError("flux must be a single (H, W) image")
@@ -417,11 +430,12 @@ class GmmHandle:
         )
 
     def prior_fwd_bwd_step(self, flux, stride, shifts, value_out, value_scale, grad_coef, step, marginalize=False,
-                           accumulate_value=False, phases=3):
+                           accumulate_value=False, phases=3, norm=None):
         """The whole prior with the component's optimizer step in the epilogue of its gather kernel
         (jd_gmm_prior_fwd_bwd_step; ``step``: a filled `_hip.Step`).  Raises RuntimeError where the library does not
         support it (stride < 4): the caller then evaluates the prior and steps separately."""
         flux = require_hip_tensor(flux, "flux")
+        self.set_image_norm(norm)
         H, W = flux.shape[-2:]
         shift_dev = None
         if isinstance(shifts, DeviceShifts):
@@ -506,7 +520,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     """Scalar GMM patch log-prior with its HIP gradient (priors/patches/core.py:227-246)."""
 
     @staticmethod
-    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale):
+    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None):
         image = require_hip_tensor(flux, "flux")
         value = torch.empty(1, dtype=torch.float32, device=image.device)
         grad = None
@@ -514,14 +528,15 @@ class GMMPatchPriorFunction(torch.autograd.Function):
             grad = torch.zeros(image.shape[-2:], dtype=torch.float32, device=image.device)
         handle.prior_fwd_bwd(
             image.reshape(image.shape[-2:]), stride, shifts, value, value_scale, grad=grad, grad_coef=value_scale,
-            marginalize=marginalize,
+            marginalize=marginalize, norm=norm,
         )
         ctx.grad, ctx.shape = grad, flux.shape
         return value.reshape(())
 
     @staticmethod
     def backward(ctx, grad_value):
-        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None
+        # (ctx.grad is the finished gradient with respect to the raw flux: the library applied the norm's chain rule)
+        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None
 
 
 class ElementwisePriorFunction(torch.autograd.Function):

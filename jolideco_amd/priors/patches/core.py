@@ -17,8 +17,13 @@ class GMMPatchPrior(Prior):
     """Patch prior: expected (max or marginal) GMM log-likelihood of all overlapping patches.
 
     Same constructor as the reference.  Options that are not on the accelerated path
-    (``cycle_spin_subpix``, ``jitter``, non-identity ``norm``, other patch norms) raise
+    (``cycle_spin_subpix``, ``jitter``, other patch norms) raise
     NotImplementedError instead of silently running something else.
+
+    ``norm``: identity, asinh, fixed-max, sigmoid, atan, log or power image norm (`utils.norms`), applied on the device in
+    front of the patch extraction; the gradient is the one with respect to the raw flux.  The norm's parameters are
+    constants of the prior (the reference trains them unless ``frozen``): they go to the kernels by value with every
+    call, and a captured epoch bakes them in.
     """
 
     shardable = True
@@ -55,8 +60,8 @@ class GMMPatchPrior(Prior):
         if self.generator.device.type != "cpu":
             raise ValueError("the cycle-spin generator must be a CPU generator")
         norm = norm if norm is not None else IdentityImageNorm()
-        if not isinstance(norm, IdentityImageNorm):
-            raise NotImplementedError("only IdentityImageNorm is implemented in jolideco_amd")
+        if not isinstance(norm, ImageNorm) or norm.device_kind is None:
+            raise NotImplementedError(f"image norm {type(norm).__name__} is not implemented in jolideco_amd")
         self.norm = norm
         patch_norm = patch_norm if patch_norm is not None else gmm.meta.patch_norm
         if not isinstance(patch_norm, SubtractMeanPatchNorm):
@@ -101,7 +106,7 @@ class GMMPatchPrior(Prior):
         shifts = self.draw_shifts()
         scale = self.log_like_weight / flux.numel()
         return GMMPatchPriorFunction.apply(
-            flux, self.gmm.handle(flux.device), self.stride, shifts, self.marginalize, scale
+            flux, self.gmm.handle(flux.device), self.stride, shifts, self.marginalize, scale, self.norm
         )
 
     def device_fwd_bwd(self, flux, value_out, grad=None, coef=0.0, patch_rows=None, shifts="draw", band_out=None, phases=3):
@@ -112,7 +117,7 @@ class GMMPatchPrior(Prior):
         scale = self.log_like_weight / flux.numel()
         self.gmm.handle(flux.device).prior_fwd_bwd(
             flux.reshape(flux.shape[-2:]), self.stride, shifts, value_out, scale, grad=grad, grad_coef=coef * scale,
-            marginalize=self.marginalize, patch_rows=patch_rows or (0, -1), band_out=band_out, phases=phases,
+            marginalize=self.marginalize, patch_rows=patch_rows or (0, -1), band_out=band_out, phases=phases, norm=self.norm,
         )
 
     # the optimizer step of the component can ride in the epilogue of this prior's last kernel (`device_fwd_bwd_step`)
@@ -130,7 +135,7 @@ class GMMPatchPrior(Prior):
         scale = self.log_like_weight / flux.numel()
         self.gmm.handle(flux.device).prior_fwd_bwd_step(
             flux.reshape(flux.shape[-2:]), self.stride, shifts, value_out, scale, coef * scale, step,
-            marginalize=self.marginalize, phases=phases,
+            marginalize=self.marginalize, phases=phases, norm=self.norm,
         )
 
     def hessian_ones(self, flux):

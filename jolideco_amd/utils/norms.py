@@ -1,15 +1,25 @@
 """Image / patch normalisations used by the GMM patch prior.
 
-Only the normalisations on the accelerated hot path are implemented: `IdentityImageNorm`
-(reference default, jolideco/utils/norms.py:225-232) and `SubtractMeanPatchNorm`
-(:97-103, fused into the HIP kernel).  Requesting any other norm raises NotImplementedError.
+Image norms (reference jolideco/utils/norms.py:225-426): identity, asinh, fixed-max, sigmoid, atan, log and power.  On
+the device the norm is one streaming pass in front of the patch kernels and its derivative rides in the gather kernel
+(csrc/gmm.hip); the classes here carry the parameters, the plain-torch evaluation (any device) and the (de)serialisation.
+``"max"`` (a global reduction) and ``"inverse-cdf"`` (a table lookup) are not implemented and raise NotImplementedError.
+Patch norms: `SubtractMeanPatchNorm` (:97-103, fused into the HIP kernel).
 """
+import numpy as np
+import torch
 
 __all__ = [
     "PatchNorm",
     "SubtractMeanPatchNorm",
     "ImageNorm",
     "IdentityImageNorm",
+    "ASinhImageNorm",
+    "FixedMaxImageNorm",
+    "SigmoidImageNorm",
+    "ATanImageNorm",
+    "LogImageNorm",
+    "PowerImageNorm",
     "NORMS_REGISTRY",
     "NORMS_PATCH_REGISTRY",
 ]
@@ -44,10 +54,24 @@ class SubtractMeanPatchNorm(PatchNorm):
 
 
 class ImageNorm:
-    """Image normalisation base class"""
+    """Image normalisation base class.
+
+    One deliberate deviation from the reference: there the parameters of a norm (alpha, beta, max_value) are
+    ``nn.Parameter``s that reach the optimizer through ``nn.Module.parameters`` unless the norm is ``frozen``.  Here they
+    are CONSTANTS of the prior -- float32 tensors without gradient, handed to the kernels by value (a captured epoch
+    bakes them in).  ``frozen`` is accepted and stored and has no other effect; results equal the reference's with the
+    norm's parameters set to ``requires_grad_(False)``.
+    """
+
+    #: kind of `jd_image_norm` (include/jolideco_hip.h); None: no device kernel
+    device_kind = None
 
     def __init__(self, frozen=False):
         self.frozen = frozen
+
+    def device_params(self):
+        """(kind, p0, p1) of `jd_image_norm`."""
+        return self.device_kind, 0.0, 0.0
 
     def to_dict(self):
         for name, cls in NORMS_REGISTRY.items():
@@ -65,9 +89,36 @@ class ImageNorm:
             return NORMS_REGISTRY[type_](**kwargs)
         return cls(**kwargs)
 
+    def __call__(self, image):
+        raise NotImplementedError
+
+    def inverse(self, image):
+        raise NotImplementedError
+
+    def evaluate_numpy(self, image):
+        """Evaluate the norm on a numpy array (float32, as the reference)"""
+        image = torch.from_numpy(np.asarray(image).astype(np.float32))
+        return self(image).detach().numpy()
+
+    def inverse_numpy(self, image):
+        """Evaluate the inverse norm on a numpy array"""
+        image = torch.from_numpy(np.asarray(image).astype(np.float32))
+        return self.inverse(image).detach().numpy()
+
+    @staticmethod
+    def _constant(value):
+        # (1,) float32, as the reference's torch.Tensor([value]): the same rounding of the parameter
+        return torch.tensor([float(value)], dtype=torch.float32)
+
+    def _p(self, name, image):
+        value = getattr(self, name)
+        return value if value.device == image.device else value.to(image.device)
+
 
 class IdentityImageNorm(ImageNorm):
     """Identity image norm"""
+
+    device_kind = 0
 
     def __call__(self, image):
         return image
@@ -76,5 +127,170 @@ class IdentityImageNorm(ImageNorm):
         return image
 
 
-NORMS_REGISTRY = {"identity": IdentityImageNorm}
+class ASinhImageNorm(ImageNorm):
+    """Inverse hyperbolic sine image norm: asinh(f / alpha) / asinh(beta / alpha)"""
+
+    device_kind = 1
+
+    def __init__(self, alpha=1.0, beta=1.0, **kwargs):
+        super().__init__(**kwargs)
+        self.alpha = self._constant(alpha)
+        self.beta = self._constant(beta)
+
+    def device_params(self):
+        return self.device_kind, float(self.alpha), float(self.beta)
+
+    def __call__(self, image):
+        alpha, beta = self._p("alpha", image), self._p("beta", image)
+        top = torch.asinh(image / alpha)
+        bottom = torch.asinh(beta / alpha)
+        return top / bottom
+
+    def inverse(self, image):
+        alpha, beta = self._p("alpha", image), self._p("beta", image)
+        value = image * torch.asinh(beta / alpha)
+        return alpha * torch.sinh(value)
+
+    def to_dict(self):
+        data = super().to_dict()
+        data["alpha"] = float(self.alpha)
+        data["beta"] = float(self.beta)
+        return data
+
+
+class FixedMaxImageNorm(ImageNorm):
+    """Fixed max image normalisation: clip(f / max_value, 0, 1)"""
+
+    device_kind = 2
+
+    def __init__(self, max_value, **kwargs):
+        super().__init__(**kwargs)
+        self.max_value = self._constant(max_value)
+
+    def device_params(self):
+        return self.device_kind, float(self.max_value), 0.0
+
+    def __call__(self, image):
+        return torch.clip(image / self._p("max_value", image), min=0, max=1)
+
+    def inverse(self, image):
+        return image * self._p("max_value", image)
+
+    def to_dict(self):
+        data = super().to_dict()
+        data["max_value"] = float(self.max_value)
+        return data
+
+
+class SigmoidImageNorm(ImageNorm):
+    """Sigmoid image normalisation: 1 / (1 + exp(-(f - beta / 2) / alpha))"""
+
+    device_kind = 3
+
+    def __init__(self, alpha=1, beta=1.0, **kwargs):
+        super().__init__(**kwargs)
+        self.alpha = self._constant(alpha)
+        self.beta = self._constant(beta)
+
+    def device_params(self):
+        return self.device_kind, float(self.alpha), float(self.beta)
+
+    def __call__(self, image):
+        alpha, beta = self._p("alpha", image), self._p("beta", image)
+        return 1 / (1 + torch.exp(-(image - beta / 2.0) / alpha))
+
+    def inverse(self, image):
+        alpha, beta = self._p("alpha", image), self._p("beta", image)
+        return alpha * torch.log(image / (1.0 - image)) + beta / 2.0
+
+    def to_dict(self):
+        data = super().to_dict()
+        data["alpha"] = float(self.alpha)
+        data["beta"] = float(self.beta)
+        return data
+
+
+class ATanImageNorm(ImageNorm):
+    """ATan image normalisation: 2 atan(f / alpha) / pi"""
+
+    device_kind = 4
+
+    def __init__(self, alpha=1, **kwargs):
+        super().__init__(**kwargs)
+        self.alpha = self._constant(alpha)
+
+    def device_params(self):
+        return self.device_kind, float(self.alpha), 0.0
+
+    def __call__(self, image):
+        return 2 * torch.atan(image / self._p("alpha", image)) / torch.pi
+
+    def inverse(self, image):
+        return 0.5 * torch.pi * torch.tan(image)  # (as the reference: without alpha)
+
+    def to_dict(self):
+        data = super().to_dict()
+        data["alpha"] = float(self.alpha)
+        return data
+
+
+class LogImageNorm(ImageNorm):
+    """Log image normalisation: log(f / alpha)"""
+
+    device_kind = 5
+
+    def __init__(self, alpha=1, **kwargs):
+        super().__init__(**kwargs)
+        self.alpha = self._constant(alpha)
+
+    def device_params(self):
+        return self.device_kind, float(self.alpha), 0.0
+
+    def __call__(self, image):
+        return torch.log(image / self._p("alpha", image))
+
+    def inverse(self, image):
+        return self._p("alpha", image) * torch.exp(image)
+
+    def to_dict(self):
+        data = super().to_dict()
+        data["alpha"] = float(self.alpha)
+        return data
+
+
+class PowerImageNorm(ImageNorm):
+    """Power image normalisation: (f / beta)^alpha"""
+
+    device_kind = 6
+
+    def __init__(self, alpha=1, beta=1, **kwargs):
+        super().__init__(**kwargs)
+        self.alpha = self._constant(alpha)
+        self.beta = self._constant(beta)
+
+    def device_params(self):
+        return self.device_kind, float(self.alpha), float(self.beta)
+
+    def __call__(self, image):
+        return torch.pow(image / self._p("beta", image), self._p("alpha", image))
+
+    def inverse(self, image):
+        return self._p("beta", image) * torch.pow(image, 1 / self._p("alpha", image))
+
+    def to_dict(self):
+        data = super().to_dict()
+        data["alpha"] = float(self.alpha)
+        data["beta"] = float(self.beta)
+        return data
+
+
+NORMS_REGISTRY = {
+    "fixed-max": FixedMaxImageNorm,
+    "sigmoid": SigmoidImageNorm,
+    "atan": ATanImageNorm,
+    "asinh": ASinhImageNorm,
+    "log": LogImageNorm,
+    "power": PowerImageNorm,
+    "identity": IdentityImageNorm,
+}
 NORMS_PATCH_REGISTRY = {"subtract-mean": SubtractMeanPatchNorm}
