@@ -268,8 +268,19 @@ int jd_conv_same_adjoint(jd_conv_plan* plan, const float* grad_out, const float*
  * jolideco/priors/patches/gmm.py: precisions_cholesky (K, D, D) (:139-149, utils/numpy.py:16-34),
  * means_precisions_cholesky (K, D) (:217-228), const_k[k] = -0.5*D*log(2*pi) + log_det_cholesky[k]
  * + log_weights[k] (:235-240,114-117,276-281) and pixel_weights (D,) (:283-299).  D must be 64
- * (8x8 patches), K <= 4096.  The library re-lays them out in MFMA fragment order with
- * sqrt(pixel_weight) folded into the columns. */
+ * (8x8 patches) or 256 (16x16 patches), K <= 4096; any other D returns JD_ERR_INVALID.  The library re-lays them out in
+ * MFMA fragment order with sqrt(pixel_weight) folded into the columns.
+ * D = 256 HANDLES (csrc/gmm256.hip) have ONE path, dense fp32 on v_mfma_f32_16x16x4_f32 -- no fp16 screen, every component
+ * is evaluated for every patch, the logsumexp is the exact one over all K -- and a narrower interface:
+ *   jd_gmm_prior_fwd_bwd       the whole image only (patch_row_begin = 0, patch_row_end = -1 or the number of patch rows)
+ *                              and the whole pass only (phases = 3); argmax_out, shift_dev, marginalize, accumulate_value and
+ *                              the handle's image norm as for D = 64; patch size 16, stride in [1, 16], H, W >= 16;
+ *   jd_gmm_estimate_log_prob   x: (n, 256);
+ *   jd_gmm_set_image_norm, jd_gmm_is_triangular, jd_gmm_screen_stats (no screened pass: generation 0), jd_gmm_destroy as for D = 64;
+ *   a patch row shard, phases 1 / 2, jd_gmm_prior_fwd_bwd_step, jd_gmm_prior_band_fwd_bwd and jd_gmm_screen_clock return
+ *   JD_ERR_INVALID with a message that names D = 256 and the refused option; nothing is launched and the handle stays
+ *   usable.  No D = 256 call ever reaches a D = 64 kernel.
+ * The fragments of a D = 256 mixture take 2 x K x 256 KB of device memory (K = 200: 105 MB). */
 int jd_gmm_create(int K, int D, const float* prec_chol, const float* mu_prec, const float* const_k,
                   const float* pixel_w, jd_gmm** gmm_out);
 int jd_gmm_destroy(jd_gmm* gmm);
@@ -395,7 +406,7 @@ int jd_add_rolled_bands_step(int H, int W, int shift_y, int shift_x, const float
                              const int* y_begin, const int* y_end, const jd_step* step, void* stream);
 
 /* (Np, K) log-probabilities of explicit patches: GaussianMixtureModel.estimate_log_prob
- * (patches/gmm.py:262-281).  x: (n, 64) device, out: (n, K) device. */
+ * (patches/gmm.py:262-281).  x: (n, D) device (D of the handle: 64 or 256), out: (n, K) device. */
 int jd_gmm_estimate_log_prob(jd_gmm* gmm, const float* x, int n, float* out, void* stream);
 
 /* Element-wise priors: InverseGammaPrior (priors/core.py:207-226; kind 1: alpha, beta) and

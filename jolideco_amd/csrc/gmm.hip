@@ -31,6 +31,8 @@
 #include "jd_common.h"
 #include "kernels.h"
 #include "jd_adam.h"
+#include "gmm_image_norm.h"
+#include "gmm256.h"
 
 namespace jd {
 
@@ -2094,56 +2096,6 @@ __global__ __launch_bounds__(256) void gmm_lse_finalize_kernel(const double* par
 // ---- image norm of the prior (jolideco/utils/norms.py:225-426; jd_image_norm of the header) ------------------------
 // n(f) is written once per pass into an image of the handle (gmm_image_norm_kernel: everything in phase 1 reads it in
 // place of the flux); n'(f) is evaluated by the gather from the pixel's RAW flux (chain rule of the overlap-add).
-enum { NORM_IDENTITY = 0, NORM_ASINH = 1, NORM_FIXED_MAX = 2, NORM_SIGMOID = 3, NORM_ATAN = 4, NORM_LOG = 5, NORM_POWER = 6,
-       NORM_COUNT = 7 };
-constexpr float NORM_PI = 3.14159265358979323846f;  // float(torch.pi)
-
-struct ImageNormArgs {
-  int kind;
-  float p0, p1;
-  float c;  // asinh: asinh(p1 / p0), the denominator (host, jd_gmm_set_image_norm); otherwise unused
-};
-
-template <int KIND>
-__device__ __forceinline__ float image_norm_value(float f, const ImageNormArgs& nm) {
-#pragma clang fp contract(off)
-  if (KIND == NORM_ASINH) return asinhf(f / nm.p0) / nm.c;
-  if (KIND == NORM_FIXED_MAX) {
-    const float t = f / nm.p0;
-    return t < 0.f ? 0.f : (t > 1.f ? 1.f : t);  // (torch.clip: a NaN stays a NaN)
-  }
-  if (KIND == NORM_SIGMOID) return 1.f / (1.f + expf(-(f - nm.p1 / 2.f) / nm.p0));
-  if (KIND == NORM_ATAN) return 2.f * atanf(f / nm.p0) / NORM_PI;
-  if (KIND == NORM_LOG) return logf(f / nm.p0);
-  if (KIND == NORM_POWER) return powf(f / nm.p1, nm.p0);
-  return f;
-}
-
-// n'(f); the kind is uniform over the launch (one scalar branch per call)
-__device__ __forceinline__ float image_norm_deriv(float f, const ImageNormArgs& nm) {
-#pragma clang fp contract(off)  // (the same bits wherever it is inlined: tiled = per-pixel gather)
-  switch (nm.kind) {
-    case NORM_ASINH: {
-      const float t = f / nm.p0;
-      return 1.f / (nm.p0 * sqrtf(1.f + t * t) * nm.c);
-    }
-    case NORM_FIXED_MAX: {
-      const float t = f / nm.p0;
-      return t >= 0.f && t <= 1.f ? 1.f / nm.p0 : 0.f;  // (inclusive ends: torch.clip's backward)
-    }
-    case NORM_SIGMOID: {
-      const float sg = 1.f / (1.f + expf(-(f - nm.p1 / 2.f) / nm.p0));
-      return sg * (1.f - sg) / nm.p0;
-    }
-    case NORM_ATAN: {
-      const float t = f / nm.p0;
-      return 2.f / (NORM_PI * nm.p0 * (1.f + t * t));
-    }
-    case NORM_LOG: return 1.f / f;
-    case NORM_POWER: return (nm.p0 / nm.p1) * powf(f / nm.p1, nm.p0 - 1.f);
-    default: return 1.f;
-  }
-}
 
 // out[i] = n(in[i]), i < n: a streaming pass (4 bytes read + 4 written per pixel), grid-stride; instantiated per kind (no
 // branch in the pixel loop).  The first 4 n4 pixels go in 16-byte loads and stores (n4 = n / 4 where both images are
@@ -2182,45 +2134,6 @@ static int launch_image_norm(const float* in, float* out, size_t n, const ImageN
   return JD_OK;
 }
 
-struct GmmGatherArgs {
-  const float* gpatch;
-  float* grad;
-  int H, W, stride, nPx, nPy, shift_y, shift_x, row_begin, row_end;  // patch-row shard
-  const int* shift_dev;  // nullable, device [2] = {shift_y, shift_x} residues: read instead of the two members above (use_device_shift)
-  int y_begin, y_end;                                                // rolled-frame pixel rows covered
-  float coef;
-  // fused backward pass (winner != nullptr and no fallback): the row of patch n is grec[winner[n]] (none if < 0)
-  const int32_t* winner;
-  const float* grec;
-  const int* flag;
-  int gen;
-  // band output (band != nullptr): instead of accumulating into `grad` at the un-rolled position, the rows
-  // [y_begin, y_end) of the ROLLED frame are written (assigned; 0 where no patch of the shard covers a pixel) to
-  // band[(Y - y_begin) * W + X] -- the compact piece a rank of a sharded prior exchanges (jd_add_rolled_bands)
-  float* band;
-  // tile kernel: W % 4 == 0 and 16-byte aligned images: the pixel groups of a thread start at X = shift_x (mod 4), so that
-  // their un-rolled column is a multiple of 4 and the gradient image is read and written with 16-byte accesses
-  int vec;
-  // fused optimizer step (do_step; tile kernel, whole image): instead of grad += coef * sum the kernel forms
-  // g = step.grad_flux[pixel] + coef * sum (the other gradient terms, read only) and applies the update of adam_kernel to
-  // the pixel -- one pass less over the gradient image and one launch less per step
-  int do_step;
-  int preload;  // do_step: the step's streams are loaded before the patch rows (JD_GMM_GATHER_PRELOAD=0: behind the barrier)
-  AdamArgs step;
-  // image norm of the pass (kind != 0: the NORM instantiations of the gather kernels): every pixel's coef * sum is
-  // multiplied by n'(raw_flux[pixel]), the rounded product (coef * sum) * n' in all three output forms; a pixel whose sum
-  // is exactly 0 receives nothing (n' may be infinite there: log norm of a zero pixel)
-  ImageNormArgs norm;
-  const float* raw_flux;
-};
-
-// (coef * sum) * n'(f), each product rounded (callers run under `fp contract(off)`); nothing for an exact zero sum
-__device__ __forceinline__ float gather_normed_term(const GmmGatherArgs& a, float sum, float f) {
-#pragma clang fp contract(off)
-  if (sum == 0.f) return 0.f;
-  const float cs = a.coef * sum;
-  return cs * image_norm_deriv(f, a.norm);
-}
 
 template <bool NORM>
 __global__ __launch_bounds__(256) void gmm_gather_kernel(GmmGatherArgs a) {
@@ -2611,6 +2524,7 @@ struct GmmPass {  // a pass between its two phases (gmm_prior_impl): what the ga
 };
 
 struct jd_gmm {
+  jd::Gmm256* d256 = nullptr;  // a D = 256 handle: everything but the image norm lives in gmm256.hip
   GmmPass pass;
   jd::ImageNormArgs norm{};  // image norm the next prior call takes (jd_gmm_set_image_norm; kind 0 = identity)
   float* normed = nullptr;   // n(flux) of the pass, (H, W): what phase 1 reads in place of the flux
@@ -2717,9 +2631,19 @@ extern "C" int jd_gmm_create(int K, int Dn, const float* prec_chol, const float*
                              const float* pixel_w, jd_gmm** gmm_out) {
   JD_REQUIRE(gmm_out && prec_chol && mu_prec && const_k && pixel_w, "jd_gmm_create: null argument");
   JD_REQUIRE(K >= 1 && K <= BUCKET_MAX_K, "jd_gmm_create: K = %d out of range [1, %d]", K, BUCKET_MAX_K);
-  JD_REQUIRE(Dn == D, "jd_gmm_create: only 8x8 patches (D = 64) are supported, got D = %d", Dn);
+  JD_REQUIRE(Dn == D || Dn == 256, "jd_gmm_create: only 8x8 and 16x16 patches (D = 64 or D = 256) are supported, got D = %d", Dn);
   jd_gmm* g = new (std::nothrow) jd_gmm();
   if (!g) return fail(JD_ERR_ALLOC, "jd_gmm_create: out of host memory");
+  if (Dn == 256) {
+    const int rc256 = gmm256_create(K, prec_chol, mu_prec, const_k, pixel_w, &g->d256);
+    if (rc256) {
+      delete g;
+      return rc256;
+    }
+    g->K = K;
+    *gmm_out = g;
+    return JD_OK;
+  }
   g->K = K;
 
   std::vector<float> afrag((size_t)K * AFRAG_FLOATS), gfrag((size_t)K * AFRAG_FLOATS), mfrag((size_t)K * 64),
@@ -2879,6 +2803,7 @@ extern "C" int jd_gmm_create(int K, int Dn, const float* prec_chol, const float*
 extern "C" int jd_gmm_destroy(jd_gmm* g) {
   if (!g) return JD_OK;
   (void)hipDeviceSynchronize();
+  if (g->d256) gmm256_destroy(g->d256), g->d256 = nullptr;  // (+ the image-norm buffer below; nothing else is allocated)
   if (g->clock_stamps) (void)hipFree(g->clock_stamps);
   if (g->normed) (void)hipFree(g->normed);
   for (float* p : {g->afrag, g->mfrag, g->const_k, g->gfrag, g->gpatch, g->vpatch})
@@ -2917,7 +2842,10 @@ extern "C" int jd_gmm_destroy(jd_gmm* g) {
   return JD_OK;
 }
 
-extern "C" int jd_gmm_is_triangular(const jd_gmm* g) { return g ? (g->triangular ? 1 : 0) : -1; }
+extern "C" int jd_gmm_is_triangular(const jd_gmm* g) {
+  if (g && g->d256) return gmm256_is_triangular(g->d256) ? 1 : 0;
+  return g ? (g->triangular ? 1 : 0) : -1;
+}
 
 // Tiles per block: the choice that minimises (rounds over the CUs) x (tiles per block); ties go to
 // the larger block (fewer fragment re-reads).
@@ -3478,6 +3406,26 @@ extern "C" int jd_gmm_prior_fwd_bwd(jd_gmm* g, const float* flux, int H, int W, 
                                     float value_scale, float* value_out, int accumulate_value, float grad_coef,
                                     float* grad_flux_accum, int32_t* argmax_out, const int* shift_dev, int phases,
                                     void* stream) {
+  if (g && g->d256) {  // 16x16 patches: the whole-image pass of gmm256.hip, or a refusal
+    JD_REQUIRE(flux && value_out, "jd_gmm_prior_fwd_bwd: null argument");
+    JD_REQUIRE(phases == 3, "jd_gmm_prior_fwd_bwd: D = 256 handles run whole passes only (phases = %d, need 3)", phases);
+    JD_REQUIRE(H >= 16 && W >= 16 && stride >= 1, "jd_gmm_prior_fwd_bwd: image (%d, %d) / stride %d not valid for D = 256", H, W, stride);
+    const int nPy256 = (H - 16) / stride + 1;
+    JD_REQUIRE(patch_row_begin == 0 && (patch_row_end < 0 || patch_row_end == nPy256),
+               "jd_gmm_prior_fwd_bwd: D = 256 handles take no patch row shard ([%d, %d) of %d rows)", patch_row_begin,
+               patch_row_end, nPy256);
+    hipStream_t s = as_stream(stream);
+    const ImageNormArgs norm = g->norm;
+    const float* image = flux;
+    if (norm.kind != NORM_IDENTITY) {
+      int rc;
+      if ((rc = grow(&g->normed, &g->normed_cap, (size_t)H * W))) return rc;
+      if ((rc = launch_image_norm(flux, g->normed, (size_t)H * W, norm, g->n_cu, s))) return rc;
+      image = g->normed;
+    }
+    return gmm256_prior(g->d256, image, flux, norm, H, W, stride, shift_y, shift_x, marginalize, value_scale, value_out,
+                        accumulate_value, grad_coef, grad_flux_accum, argmax_out, shift_dev, s);
+  }
   return gmm_prior_impl(g, flux, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, value_scale,
                         value_out, accumulate_value, grad_coef, grad_flux_accum, argmax_out, nullptr, stream, nullptr, shift_dev,
                         phases);
@@ -3499,6 +3447,7 @@ extern "C" int jd_gmm_screen_stats(const jd_gmm* g, int* out) {
 // ticks) over the blocks that have left stamps since the last call, and clears them.
 extern "C" int jd_gmm_screen_clock(jd_gmm* g, double* mhz_out, int* samples_out) {
   JD_REQUIRE(g && mhz_out && samples_out, "jd_gmm_screen_clock: null argument");
+  JD_REQUIRE(!g->d256, "jd_gmm_screen_clock: D = 256 handles have no screen kernel");
   *mhz_out = 0.0, *samples_out = 0;
   const size_t bytes = (size_t)2 * SCREEN_CLOCK_CAP * sizeof(unsigned long long);
   if (!g->clock_stamps) {
@@ -3523,6 +3472,7 @@ extern "C" int jd_gmm_prior_fwd_bwd_step(jd_gmm* g, const float* flux, int H, in
                                          int marginalize, float value_scale, float* value_out, int accumulate_value,
                                          float grad_coef, const jd_step* step, const int* shift_dev, int phases,
                                          void* stream) {
+  JD_REQUIRE(!(g && g->d256), "jd_gmm_prior_fwd_bwd_step: D = 256 handles have no fused optimizer step");
   JD_REQUIRE(step && step->theta && step->flux_in && step->flux_out && step->grad_flux, "jd_gmm_prior_fwd_bwd_step: null argument");
   JD_REQUIRE(step->sgd || (step->exp_avg && step->exp_avg_sq), "jd_gmm_prior_fwd_bwd_step: Adam needs its moment images");
   AdamArgs a{};
@@ -3539,6 +3489,7 @@ extern "C" int jd_gmm_prior_band_fwd_bwd(jd_gmm* g, const float* flux, int H, in
                                          int shift_x, int patch_row_begin, int patch_row_end, int marginalize,
                                          float value_scale, float* value_out, int accumulate_value, float grad_coef,
                                          float* band_out, void* stream) {
+  JD_REQUIRE(!(g && g->d256), "jd_gmm_prior_band_fwd_bwd: D = 256 handles have no band output");
   JD_REQUIRE(band_out, "jd_gmm_prior_band_fwd_bwd: null band");
   return gmm_prior_impl(g, flux, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, value_scale,
                         value_out, accumulate_value, grad_coef, nullptr, nullptr, band_out, stream);
@@ -3603,6 +3554,7 @@ extern "C" int jd_add_rolled_bands_step(int H, int W, int shift_y, int shift_x, 
 extern "C" int jd_gmm_estimate_log_prob(jd_gmm* g, const float* x, int n, float* out, void* stream) {
   JD_REQUIRE(g && x && out && n > 0, "jd_gmm_estimate_log_prob: null argument or n <= 0");
   hipStream_t s = as_stream(stream);
+  if (g->d256) return gmm256_estimate_log_prob(g->d256, x, n, out, s);
   int rc;
   if ((rc = grow(&g->partials, &g->partials_cap, (size_t)((n + 31) / 32 + 4)))) return rc;
   GmmFwdArgs a{};

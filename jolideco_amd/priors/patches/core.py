@@ -16,7 +16,8 @@ log = logging.getLogger(__name__)
 class GMMPatchPrior(Prior):
     """Patch prior: expected (max or marginal) GMM log-likelihood of all overlapping patches.
 
-    Same constructor as the reference.  Options that are not on the accelerated path
+    Same constructor as the reference.  8x8 and 16x16 patches (64 / 256 features) have kernels; a 16x16 prior runs the
+    whole-image dense pass only (`shardable`, `supports_fused_step`, `supports_phases` are False for it).  Options that are not on the accelerated path
     (``cycle_spin_subpix``, ``jitter``, other patch norms) raise
     NotImplementedError instead of silently running something else.
 
@@ -25,8 +26,6 @@ class GMMPatchPrior(Prior):
     constants of the prior (the reference trains them unless ``frozen``): they go to the kernels by value with every
     call, and a captured epoch bakes them in.
     """
-
-    shardable = True
 
     def __init__(
         self,
@@ -76,6 +75,28 @@ class GMMPatchPrior(Prior):
         return self.gmm.patch_shape
 
     @property
+    def _full_path(self):
+        """8x8 patches run every form of the pass; 16x16 patches (D = 256) have the whole-image dense pass only."""
+        return tuple(self.patch_shape) == (8, 8)
+
+    @property
+    def shardable(self):
+        """The patch rows can be split over the ranks of a sharded joint fit (band output).  A prior that cannot is
+        evaluated whole on rank 0, like the element-wise priors (`FitSession`)."""
+        return self._full_path
+
+    @property
+    def supports_fused_step(self):
+        """The optimizer step of the component can ride in the epilogue of this prior's last kernel (`device_fwd_bwd_step`)."""
+        return self._full_path
+
+    @property
+    def supports_phases(self):
+        """The pass splits into phase 1 (value + gradient rows: reads the flux only) and phase 2 (gather [+ step]): phase 1
+        may run on a second stream beside the likelihood launches (`phases` of device_fwd_bwd[_step]; FitSession)."""
+        return self._full_path
+
+    @property
     def overlap(self):
         return max(self.patch_shape) - self.stride
 
@@ -119,12 +140,6 @@ class GMMPatchPrior(Prior):
             flux.reshape(flux.shape[-2:]), self.stride, shifts, value_out, scale, grad=grad, grad_coef=coef * scale,
             marginalize=self.marginalize, patch_rows=patch_rows or (0, -1), band_out=band_out, phases=phases, norm=self.norm,
         )
-
-    # the optimizer step of the component can ride in the epilogue of this prior's last kernel (`device_fwd_bwd_step`)
-    supports_fused_step = True
-    # the pass splits into phase 1 (value + gradient rows: reads the flux only) and phase 2 (gather [+ step]): phase 1 may run
-    # on a second stream beside the likelihood launches (`phases` of device_fwd_bwd[_step]; FitSession)
-    supports_phases = True
 
     def device_fwd_bwd_step(self, flux, value_out, coef, step, shifts="draw", phases=3):
         """`device_fwd_bwd` of the WHOLE prior with the component's optimizer step applied by its gather kernel:
