@@ -415,6 +415,26 @@ int jd_gmm_estimate_log_prob(jd_gmm* gmm, const float* x, int n, float* out, voi
 int jd_elementwise_prior_fwd_bwd(int kind, const float* flux, size_t n, float alpha, float beta,
                                  float log_const, float* value_out, float grad_coef,
                                  float* grad_flux_accum, void* stream);
+/* The same priors with `cycle_spin_subpix=True` (priors/core.py:220-221,321-322; utils/torch.py:31-38,122-143): the prior
+ * is evaluated on s = K (*) flux, the 3 x 3 cross-correlation ("same", zero outside the (H, W) image) with
+ * k[i][j] = wx(j - 1) * wy(i - 1), w(t) = 1 - |t - o| where |t - o| < 1 else 0 for the offsets o = x0, y0 in [-0.5, 0.5]
+ * that the caller drew (x0 first); the weights are formed in the kernel in the reference's float32 operations.
+ * value_out <- sum(v(s)) / (H W) + log_const;  grad_flux_accum += grad_coef * K^T v'(s) (NULL: value only).
+ * One launch over 2-D tiles (flux tile + halo staged in LDS, one read-modify-write of the gradient per pixel, no atomics:
+ * run-to-run identical) plus the fixed-order sum of the block partials.
+ * offset_dev != NULL: device [2] = {x0, y0}, read by the kernel instead of the two by-value arguments (see
+ * jd_gmm_prior_fwd_bwd: device-resident step scalars).  By-value offsets outside [-0.5, 0.5] or not finite, a kind other
+ * than 1 / 2, a NULL flux or value_out and a non-positive shape return JD_ERR_INVALID. */
+int jd_elementwise_prior_subpix_fwd_bwd(int kind, const float* flux, int H, int W, float alpha, float beta,
+                                        float log_const, float x0, float y0, const float* offset_dev,
+                                        float* value_out, float grad_coef, float* grad_flux_accum, void* stream);
+/* SmoothnessPrior (priors/core.py:373-384): value_out <- -sum(flux * (K (*) flux)) for the kernel whose operator `khat`
+ * jd_conv_psf_spectrum built for `plan` (the plan's (H, W) is the image; "same" zero-padded convolution, no division by
+ * the number of pixels);  grad_flux_accum += grad_coef * (-2 K (*) flux) (NULL: value only) -- K is symmetric and odd-sized,
+ * so the operator is its own adjoint.  Runs jd_conv_same into a scratch image of the library (grown on the first call of a
+ * size: not inside a captured region) and one streaming launch behind it. */
+int jd_smoothness_prior_fwd_bwd(jd_conv_plan* plan, const float* khat, const float* flux, float* value_out,
+                                float grad_coef, float* grad_flux_accum, void* stream);
 
 /* Parameter update -------------------------------------------------------------------------
  * flux = exp(theta) [* mask]   (SpatialFluxComponent.flux_upsampled, models/core.py:583-594);
@@ -489,7 +509,10 @@ enum {
   JD_KERNEL_GMM_STAGE = 15,      /*   stage 0: patches -> mean-subtracted fp16 fragments, norms, scales (inside GMM_FWD) */
   JD_KERNEL_SHIFT = 16,          /* calibration: bilinear sub-pixel shift and its transpose (+ shift gradient partial sums) */
   JD_KERNEL_POISSON_MIXED = 17,  /* K3 for components of different up-sampling factors: pool + clip + NLL + replicated gradient */
-  JD_KERNEL_COUNT = 18
+  JD_KERNEL_ELEMENTWISE_SUBPIX = 18, /* element-wise priors with sub-pixel cycle spin: stencil + value + adjoint stencil */
+  JD_KERNEL_SMOOTHNESS = 19,     /* smoothness prior: sum f (K * f) and its gradient behind the convolution */
+  JD_KERNEL_ELEMENTWISE_PRIOR = 20, /* element-wise priors (inverse-gamma, exponential): value + gradient */
+  JD_KERNEL_COUNT = 21
 };
 int jd_profile_enable(int capacity);
 int jd_profile_disable(void);

@@ -19,6 +19,7 @@ from .priors import (
     GMMPatchPrior,
     InverseGammaPrior,
     Priors,
+    SmoothnessPrior,
     UniformPrior,
 )
 
@@ -41,5 +42,6 @@ __all__ = [
     "UniformPrior",
     "InverseGammaPrior",
     "ExponentialPrior",
+    "SmoothnessPrior",
     "Priors",
 ]

@@ -106,6 +106,12 @@ EXPORTS = {
         c_int,
         [c_int, c_void_p, c_size_t, c_float, c_float, c_float, c_void_p, c_float, c_void_p, c_void_p],
     ),
+    "jd_elementwise_prior_subpix_fwd_bwd": (
+        c_int,
+        [c_int, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_float, c_void_p,
+         c_void_p],
+    ),
+    "jd_smoothness_prior_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "jd_flux_from_theta": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "jd_sum_images": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p]),
     "jd_copy_image_to": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p]),
@@ -150,7 +156,7 @@ KERNEL_IDS = {
     "poisson_fused": 0, "gmm_fwd": 1, "gmm_bwd": 2, "gmm_gather": 3, "pad_mul": 4, "cmul": 5,
     "adjoint_epilogue": 6, "adam": 7, "fft_r2c": 8, "fft_c2r": 9, "direct_conv": 10, "sep_conv": 11,
     "gmm_screen": 12, "gmm_sort": 13, "gmm_exact": 14, "gmm_stage": 15, "shift": 16,
-    "poisson_mixed": 17,
+    "poisson_mixed": 17, "elementwise_subpix": 18, "smoothness": 19, "elementwise_prior": 20,
 }
 
 _lib = None

@@ -839,7 +839,10 @@ class FitSession:
         cached = getattr(self, "_plan_slots_cache", None)
         if cached is not None:
             return cached
-        drawing = [ci for ci, prior in enumerate(self.priors) if hasattr(prior, "draw_shifts")]
+        # (priors whose evaluations draw from a generator: the GMM prior's cycle-spin rolls, the sparse priors' sub-pixel
+        # offsets when that option is on -- `draws_shifts` False leaves a prior out)
+        drawing = [ci for ci, prior in enumerate(self.priors)
+                   if hasattr(prior, "draw_shifts") and getattr(prior, "draws_shifts", True)]
         n_local = len(self.local_idx)
         if self.joint:
             n_shift = len(drawing)
@@ -871,29 +874,28 @@ class FitSession:
         adam = cfg.optimizer_type == "adam"
         n_eval = 1 if self.joint else len(self.local_idx) + 1
         shifts_host, shifts = [], []
+
+        def place(ci, drawn):
+            """The next two-word slot for the draw of prior `ci`: the roll residues of a cycle spin, or the float32 bit
+            patterns of the (x0, y0) of a sub-pixel cycle spin (the way the bias terms travel)."""
+            slot = sc.shift_slots[len(shifts_host)]
+            if drawn is None:
+                shifts_host.append((0, 0))
+                return None
+            if getattr(self.priors[ci], "shift_kind", "roll") == "subpixel":
+                shifts_host.append(tuple(int(b) for b in np.asarray(drawn, dtype=np.float32).view(np.int32)))
+                return DeviceShifts(slot.view(torch.float32), drawn)
+            H, W = self.states[ci].shape
+            shifts_host.append((drawn[0] % H, drawn[1] % W))
+            return DeviceShifts(slot, drawn)
+
         if len(drawing) == 1:  # one drawing prior: all draws of the epoch in one call (same numbers, same generator state)
             ci = drawing[0]
-            prior, (H, W) = self.priors[ci], self.states[ci].shape
-            for drawn in prior.draw_shifts_many(n_eval):
-                if drawn is None:
-                    shifts.append({ci: None})
-                    shifts_host.append((0, 0))
-                else:
-                    shifts.append({ci: DeviceShifts(sc.shift_slots[len(shifts_host)], drawn)})
-                    shifts_host.append((drawn[0] % H, drawn[1] % W))
+            for drawn in self.priors[ci].draw_shifts_many(n_eval):
+                shifts.append({ci: place(ci, drawn)})
         else:
             for _ in range(n_eval):
-                row = {}
-                for ci in drawing:
-                    prior, (H, W) = self.priors[ci], self.states[ci].shape
-                    drawn = prior.draw_shifts()
-                    if drawn is None:
-                        row[ci] = None
-                        shifts_host.append((0, 0))
-                    else:
-                        row[ci] = DeviceShifts(sc.shift_slots[len(shifts_host)], drawn)
-                        shifts_host.append((drawn[0] % H, drawn[1] % W))
-                shifts.append(row)
+                shifts.append({ci: place(ci, self.priors[ci].draw_shifts()) for ci in drawing})
         biases = [adam_bias_terms(self.step + j + 1, lr, beta1, beta2) if adam else (0.0, 1.0) for j in range(n_flux)]
         flux_bias = [sc.bias_slots[j] if adam else None for j in range(n_flux)]
         cal_bias, cal_items, k = [], [], n_flux

@@ -744,6 +744,182 @@ __global__ __launch_bounds__(BLOCK) void elementwise_prior_kernel(int kind, cons
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
+// ------------------------------------------------------------------------------------------
+// element-wise priors with sub-pixel cycle spin (priors/core.py:220-226,321-326; utils/torch.py:31-38,122-143): the
+// prior is evaluated on s = K (*) f, the 3 x 3 cross-correlation of the flux with the bilinear weights of a shift
+// (x0, y0) in [-0.5, 0.5]^2, zero outside the image; the gradient is the adjoint stencil of g = v'(s).  One launch over
+// 2-D tiles of SP_TY x SP_TX pixels: a block stages its flux tile with a 2-pixel halo in LDS, forms s and g on the tile
+// plus a 1-pixel halo (g = 0 outside the image; the halo is computed again by the neighbouring block, so no block reads
+// another's results), applies the adjoint stencil from LDS and does ONE read-modify-write of grad per pixel it owns.
+// v(s) is summed over the owned pixels only, into one double per block.  HBM traffic: 12 B/pixel (the halo re-reads
+// come from L2), like elementwise_prior_kernel.
+// ------------------------------------------------------------------------------------------
+// tile height, measured on MI355X (inverse-gamma, us per launch): 2048^2 32 rows 22.6, 16 rows 24.4, 8 rows 23.8;
+// 8192^2 203 / 220 / 282 (profiles/priors/README.md)
+constexpr int SP_TX = 64, SP_TY = 32;
+constexpr int SP_FW = SP_TX + 4, SP_FH = SP_TY + 4;  // flux window: tile + 2-pixel halo
+constexpr int SP_GW = SP_TX + 2, SP_GH = SP_TY + 2;  // s / g window: tile + 1-pixel halo
+
+struct SubpixArgs {
+  const float* flux;
+  float* grad;  // nullable: value only
+  double* partials;
+  const float* offset_dev;  // nullable, device [2] = {x0, y0}: read instead of the two members below
+  float x0, y0;
+  float alpha, beta, coef;
+  int kind, H, W;
+};
+
+// k[i][j] = wx(j - 1) * wy(i - 1), w(t) = 1 - |t - o| where |t - o| < 1, else 0: the float32 operations of
+// `grid_weights`, one by one (no contraction), so the weights carry the reference's bits
+__device__ __forceinline__ void subpix_weights(float x0, float y0, float (&k)[3][3]) {
+#pragma clang fp contract(off)
+  float wx[3], wy[3];
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const float dx = fabsf((float)(t - 1) - x0), dy = fabsf((float)(t - 1) - y0);
+    wx[t] = dx < 1.f ? 1.f - dx : 0.f;
+    wy[t] = dy < 1.f ? 1.f - dy : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) k[i][j] = wx[j] * wy[i];
+}
+
+// VEC: W % 4 == 0 and 16-byte aligned images -- the 64 columns of the tile go in 16-byte loads, the read-modify-write of
+// grad in 16-byte loads and stores (a group of 4 columns is then inside the image or outside as a whole)
+template <bool VEC>
+__global__ __launch_bounds__(BLOCK) void elementwise_prior_subpix_kernel(SubpixArgs a) {
+  __shared__ float F[SP_FH][SP_FW];
+  __shared__ float G[SP_GH][SP_GW];
+  __shared__ double smem[BLOCK / 64];
+  const int H = a.H, W = a.W;
+  const int tx0 = blockIdx.x * SP_TX, ty0 = blockIdx.y * SP_TY;  // first owned pixel
+  const float x0 = a.offset_dev ? a.offset_dev[0] : a.x0, y0 = a.offset_dev ? a.offset_dev[1] : a.y0;
+  float k[3][3];
+  subpix_weights(x0, y0, k);
+
+  // ---- flux window -> LDS (zero outside the image) ----
+  const int c4 = threadIdx.x & 15, r0 = threadIdx.x >> 4;  // column group of 4, row 0..15
+  for (int r = r0; r < SP_FH; r += 16) {
+    const int y = ty0 - 2 + r, x = tx0 + 4 * c4;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (y >= 0 && y < H) {
+      const float* row = a.flux + (size_t)y * W;
+      if (VEC) {
+        if (x < W) {
+          const float4 q = *reinterpret_cast<const float4*>(row + x);
+          v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (x + i < W) v[i] = row[x + i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) F[r][2 + 4 * c4 + i] = v[i];
+  }
+  if (threadIdx.x < 4 * SP_FH) {  // the two halo columns either side
+    const int r = threadIdx.x >> 2, c = threadIdx.x & 3;
+    const int col = c < 2 ? c : SP_TX + c;  // 0, 1, TX + 2, TX + 3
+    const int y = ty0 - 2 + r, x = tx0 - 2 + col;
+    F[r][col] = (y >= 0 && y < H && x >= 0 && x < W) ? a.flux[(size_t)y * W + x] : 0.f;
+  }
+  __syncthreads();
+
+  // ---- s = K (*) f and g = v'(s) on the tile + 1-pixel halo; v(s) summed over the owned pixels ----
+  double local = 0.0;
+  const float am1 = -a.alpha - 1.f;
+  for (int idx = threadIdx.x; idx < SP_GH * SP_GW; idx += BLOCK) {
+    const int ry = idx / SP_GW, rx = idx - ry * SP_GW;
+    const int y = ty0 - 1 + ry, x = tx0 - 1 + rx;
+    float g = 0.f;
+    if (y >= 0 && y < H && x >= 0 && x < W) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s = fmaf(k[i][j], F[ry + i][rx + j], s);
+      float value;
+      if (a.kind == 1) {  // inverse gamma: the expressions of elementwise_prior_kernel
+        value = -a.beta / s + am1 * logf(s);
+        g = a.beta / (s * s) + am1 / s;
+      } else {
+        value = -a.alpha * s;
+        g = -a.alpha;
+      }
+      if (ry >= 1 && ry <= SP_TY && rx >= 1 && rx <= SP_TX) local += (double)value;
+    }
+    G[ry][rx] = g;
+  }
+  __syncthreads();
+
+  // ---- adjoint stencil: df[p][q] = sum_ij k[i][j] g[p - i + 1][q - j + 1]; grad += coef * df ----
+  if (a.grad) {
+    for (int r = r0; r < SP_TY; r += 16) {
+      const int y = ty0 + r, x = tx0 + 4 * c4;
+      if (y >= H || x >= W) continue;
+      float df[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        float gr[6];  // g[y - i + 1][x - 1 .. x + 4]: window row (r + 1) - i + 1, columns 4 c4 .. 4 c4 + 5
+#pragma unroll
+        for (int c = 0; c < 6; ++c) gr[c] = G[r + 2 - i][4 * c4 + c];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) df[e] = fmaf(k[i][j], gr[e + 2 - j], df[e]);
+      }
+      float* dst = a.grad + (size_t)y * W + x;
+      if (VEC) {
+        float4 q = *reinterpret_cast<float4*>(dst);
+        q.x += a.coef * df[0], q.y += a.coef * df[1], q.z += a.coef * df[2], q.w += a.coef * df[3];
+        *reinterpret_cast<float4*>(dst) = q;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (x + e < W) dst[e] += a.coef * df[e];
+      }
+    }
+  }
+  const double total = block_sum<BLOCK>(local, smem);
+  if (threadIdx.x == 0) a.partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// ------------------------------------------------------------------------------------------
+// smoothness prior epilogue (priors/core.py:373-384): with s = K (*) f already in `smooth`, the partial sums of f * s
+// (value = -sum f s) and grad += coef * s, coef = grad_coef * (-2) (K symmetric: the operator is self-adjoint).  A
+// streaming pass, 16 B/pixel with the gradient: the first 4 n4 pixels in 16-byte accesses (n4 = n / 4 where all images are
+// 16-byte aligned, else 0), the tail pixel by pixel.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void smoothness_prior_kernel(const float* __restrict__ flux,
+                                                                const float* __restrict__ smooth, size_t n, size_t n4,
+                                                                float coef, float* __restrict__ grad,
+                                                                double* __restrict__ partials) {
+  __shared__ double smem[BLOCK / 64];
+  const size_t tid = (size_t)blockIdx.x * BLOCK + threadIdx.x, nthreads = (size_t)gridDim.x * BLOCK;
+  double local = 0.0;
+  for (size_t i = tid; i < n4; i += nthreads) {
+    const float4 f = reinterpret_cast<const float4*>(flux)[i];
+    const float4 s = reinterpret_cast<const float4*>(smooth)[i];
+    local += (double)(f.x * s.x) + (double)(f.y * s.y) + (double)(f.z * s.z) + (double)(f.w * s.w);
+    if (grad) {
+      float4 g = reinterpret_cast<float4*>(grad)[i];
+      g.x += coef * s.x, g.y += coef * s.y, g.z += coef * s.z, g.w += coef * s.w;
+      reinterpret_cast<float4*>(grad)[i] = g;
+    }
+  }
+  for (size_t i = 4 * n4 + tid; i < n; i += nthreads) {
+    const float s = smooth[i];
+    local += (double)(flux[i] * s);
+    if (grad) grad[i] += coef * s;
+  }
+  const double total = block_sum<BLOCK>(local, smem);
+  if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
 // small per-process scratch for the stand-alone reductions (grown on demand, never freed while
 // the library is loaded; one per device would be needed for multi-device processes -- the
 // framework runs one process per GPU)
@@ -790,10 +966,77 @@ extern "C" int jd_elementwise_prior_fwd_bwd(int kind, const float* flux, size_t 
   int rc = ensure_partials(8192);
   if (rc) return rc;
   hipStream_t s = as_stream(stream);
-  elementwise_prior_kernel<<<(unsigned)blocks, BLOCK, 0, s>>>(kind, flux, n, alpha, beta, grad_coef,
-                                                             grad_flux_accum, g_partials);
+  {
+    ProfScope prof(JD_KERNEL_ELEMENTWISE_PRIOR, s);
+    elementwise_prior_kernel<<<(unsigned)blocks, BLOCK, 0, s>>>(kind, flux, n, alpha, beta, grad_coef,
+                                                               grad_flux_accum, g_partials);
+  }
   JD_LAUNCH_CHECK();
   return launch_finalize_sum(g_partials, (int)blocks, 1.0 / (double)n, (double)log_const, value_out, 0, s);
+}
+
+extern "C" int jd_elementwise_prior_subpix_fwd_bwd(int kind, const float* flux, int H, int W, float alpha, float beta,
+                                                   float log_const, float x0, float y0, const float* offset_dev,
+                                                   float* value_out, float grad_coef, float* grad_flux_accum,
+                                                   void* stream) {
+  JD_REQUIRE(kind == 1 || kind == 2,
+             "jd_elementwise_prior_subpix_fwd_bwd: kind must be 1 (inverse-gamma) or 2 (exponential)");
+  JD_REQUIRE(flux && value_out && H > 0 && W > 0, "jd_elementwise_prior_subpix_fwd_bwd: null argument or non-positive shape");
+  // (the negated form refuses NaN too)
+  JD_REQUIRE(offset_dev || (x0 >= -0.5f && x0 <= 0.5f && y0 >= -0.5f && y0 <= 0.5f),
+             "jd_elementwise_prior_subpix_fwd_bwd: offsets (%g, %g) not in [-0.5, 0.5]", (double)x0, (double)y0);
+  const dim3 grid((W + SP_TX - 1) / SP_TX, (H + SP_TY - 1) / SP_TY);
+  const size_t blocks = (size_t)grid.x * grid.y;
+  JD_REQUIRE(blocks <= (size_t)1 << 24 && grid.y <= 65535, "jd_elementwise_prior_subpix_fwd_bwd: image %d x %d too large", H, W);
+  int rc = ensure_partials(blocks > 8192 ? blocks : 8192);
+  if (rc) return rc;
+  hipStream_t s = as_stream(stream);
+  SubpixArgs a{flux, grad_flux_accum, g_partials, offset_dev, x0, y0, alpha, beta, grad_coef, kind, H, W};
+  const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(flux) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(grad_flux_accum) & 15) == 0;
+  {
+    ProfScope prof(JD_KERNEL_ELEMENTWISE_SUBPIX, s);
+    if (vec)
+      elementwise_prior_subpix_kernel<true><<<grid, BLOCK, 0, s>>>(a);
+    else
+      elementwise_prior_subpix_kernel<false><<<grid, BLOCK, 0, s>>>(a);
+  }
+  JD_LAUNCH_CHECK();
+  return launch_finalize_sum(g_partials, (int)blocks, 1.0 / ((double)H * (double)W), (double)log_const, value_out, 0, s);
+}
+
+// scratch image of the smoothness prior (K (*) f), grown on demand like g_partials
+static float* g_smooth = nullptr;
+static size_t g_smooth_cap = 0;
+
+extern "C" int jd_smoothness_prior_fwd_bwd(jd_conv_plan* plan, const float* khat, const float* flux, float* value_out,
+                                           float grad_coef, float* grad_flux_accum, void* stream) {
+  JD_REQUIRE(plan && khat && flux && value_out, "jd_smoothness_prior_fwd_bwd: null argument");
+  int shape[6];
+  int rc = jd_conv_plan_shape(plan, shape);
+  if (rc) return rc;
+  const size_t n = (size_t)shape[0] * (size_t)shape[1];
+  if (n > g_smooth_cap) {
+    if (g_smooth) (void)hipFree(g_smooth);
+    g_smooth = nullptr, g_smooth_cap = 0;
+    JD_HIP(hipMalloc(&g_smooth, n * sizeof(float)));
+    g_smooth_cap = n;
+  }
+  if ((rc = ensure_partials(8192))) return rc;
+  if ((rc = jd_conv_same(plan, flux, nullptr, khat, g_smooth, stream))) return rc;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(flux) | reinterpret_cast<uintptr_t>(grad_flux_accum)) & 15) == 0;
+  const size_t n4 = aligned ? n / 4 : 0;
+  size_t blocks = (n4 + (n - 4 * n4) + BLOCK - 1) / BLOCK;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipStream_t s = as_stream(stream);
+  {
+    ProfScope prof(JD_KERNEL_SMOOTHNESS, s);
+    smoothness_prior_kernel<<<(unsigned)blocks, BLOCK, 0, s>>>(flux, g_smooth, n, n4, -2.f * grad_coef, grad_flux_accum,
+                                                              g_partials);
+  }
+  JD_LAUNCH_CHECK();
+  return launch_finalize_sum(g_partials, (int)blocks, -1.0, 0.0, value_out, 0, s);
 }
 
 extern "C" int jd_flux_from_theta(const float* theta, const float* mask, float* flux, size_t n, int use_log_flux,

@@ -158,6 +158,9 @@ extern "C" const char* jd_kernel_name(int kernel) {
     case JD_KERNEL_GMM_STAGE: return "gmm_stage_kernel";
     case JD_KERNEL_SHIFT: return "shift_kernels";
     case JD_KERNEL_POISSON_MIXED: return "poisson_mixed_kernel";
+    case JD_KERNEL_ELEMENTWISE_SUBPIX: return "elementwise_prior_subpix_kernel";
+    case JD_KERNEL_SMOOTHNESS: return "smoothness_prior_kernel";
+    case JD_KERNEL_ELEMENTWISE_PRIOR: return "elementwise_prior_kernel";
     default: return "?";
   }
 }

@@ -23,6 +23,7 @@ __all__ = [
     "PoissonNLLFunction",
     "GMMPatchPriorFunction",
     "ElementwisePriorFunction",
+    "SmoothnessPriorFunction",
     "stirling_mean",
     "require_hip_tensor",
     "band_rows",
@@ -335,7 +336,8 @@ class ConvPlan:
 
 class DeviceShifts:
     """Cycle-spin shifts of one prior evaluation held in DEVICE memory: ``dev`` = int32 tensor [shift_y mod H, shift_x mod W]
-    the kernels read (jd_gmm_prior_fwd_bwd: device-resident step scalars), ``host`` = the same pair as the host drew it."""
+    the kernels read (jd_gmm_prior_fwd_bwd: device-resident step scalars), ``host`` = the same pair as the host drew it.
+    For a sub-pixel cycle spin ``dev`` is a float32 view of the slot holding [x0, y0] (jd_elementwise_prior_subpix_fwd_bwd)."""
 
     __slots__ = ("dev", "host")
 
@@ -539,26 +541,78 @@ class GMMPatchPriorFunction(torch.autograd.Function):
         return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None
 
 
+def elementwise_prior_subpix(kind, flux, alpha, beta, log_const, shifts, value_out, grad_coef, grad=None):
+    """InverseGammaPrior / ExponentialPrior with sub-pixel cycle spin (jd_elementwise_prior_subpix_fwd_bwd): the prior on
+    the 3 x 3 stencil of ``shifts`` = (x0, y0) -- or a `DeviceShifts` whose ``dev`` holds them as two float32 in device
+    memory (planned epochs).  value -> ``value_out``; ``grad += grad_coef * d sum(v) / d flux`` when ``grad`` is given."""
+    flux = require_hip_tensor(flux, "flux")
+    H, W = flux.shape[-2:]
+    if flux.numel() != H * W:
+        raise ValueError("flux must be a single (H, W) image")
+    offset_dev = None
+    if isinstance(shifts, DeviceShifts):
+        offset_dev, shifts = ptr(shifts.dev), shifts.host
+    x0, y0 = shifts
+    check(
+        _hip.lib().jd_elementwise_prior_subpix_fwd_bwd(
+            int(kind), ptr(flux), int(H), int(W), c_float(alpha), c_float(beta), c_float(log_const), c_float(x0), c_float(y0),
+            offset_dev, ptr(value_out), c_float(grad_coef), ptr(grad), stream_ptr(flux.device),
+        )
+    )
+
+
 class ElementwisePriorFunction(torch.autograd.Function):
-    """InverseGammaPrior / ExponentialPrior value and gradient (priors/core.py:207-226,308-326)."""
+    """InverseGammaPrior / ExponentialPrior value and gradient (priors/core.py:207-226,308-326); ``shifts`` = (x0, y0):
+    the sub-pixel cycle-spin form."""
 
     @staticmethod
-    def forward(ctx, flux, kind, alpha, beta, log_const):
+    def forward(ctx, flux, kind, alpha, beta, log_const, shifts=None):
         image = require_hip_tensor(flux, "flux")
         value = torch.empty(1, dtype=torch.float32, device=image.device)
         grad = torch.zeros_like(image) if flux.requires_grad else None
-        check(
-            _hip.lib().jd_elementwise_prior_fwd_bwd(
-                int(kind), ptr(image), image.numel(), c_float(alpha), c_float(beta), c_float(log_const), ptr(value),
-                c_float(1.0 / image.numel()), ptr(grad), stream_ptr(image.device),
+        if shifts is not None:
+            elementwise_prior_subpix(kind, image, alpha, beta, log_const, shifts, value, 1.0 / image.numel(), grad)
+        else:
+            check(
+                _hip.lib().jd_elementwise_prior_fwd_bwd(
+                    int(kind), ptr(image), image.numel(), c_float(alpha), c_float(beta), c_float(log_const), ptr(value),
+                    c_float(1.0 / image.numel()), ptr(grad), stream_ptr(image.device),
+                )
             )
-        )
         ctx.grad, ctx.shape = grad, flux.shape
         return value.reshape(())
 
     @staticmethod
     def backward(ctx, grad_value):
-        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None
+        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None
+
+
+def smoothness_prior(plan, khat, flux, value_out, grad_coef=0.0, grad=None):
+    """SmoothnessPrior (jd_smoothness_prior_fwd_bwd): value_out <- -sum(flux * (K (*) flux)),
+    ``grad += grad_coef * (-2 K (*) flux)`` when ``grad`` is given; ``khat``: the kernel's operator for ``plan``."""
+    flux = plan._check_image(flux, "flux")
+    check(
+        _hip.lib().jd_smoothness_prior_fwd_bwd(
+            plan._handle, ptr(khat), ptr(flux), ptr(value_out), c_float(grad_coef), ptr(grad), stream_ptr(flux.device),
+        )
+    )
+
+
+class SmoothnessPriorFunction(torch.autograd.Function):
+    """SmoothnessPrior value with its HIP gradient (priors/core.py:382-384)."""
+
+    @staticmethod
+    def forward(ctx, flux, plan, khat):
+        image = require_hip_tensor(flux, "flux")
+        value = torch.empty(1, dtype=torch.float32, device=image.device)
+        grad = torch.zeros_like(image) if flux.requires_grad else None
+        smoothness_prior(plan, khat, image, value, 1.0, grad)
+        ctx.grad, ctx.shape = grad, flux.shape
+        return value.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_value):
+        return (ctx.grad * grad_value).reshape(ctx.shape), None, None
 
 
 def band_rows(patch_rows, stride, H, patch=8):

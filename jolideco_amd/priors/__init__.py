@@ -1,4 +1,4 @@
-from .core import ExponentialPrior, InverseGammaPrior, Prior, Priors, UniformPrior
+from .core import ExponentialPrior, InverseGammaPrior, Prior, Priors, SmoothnessPrior, UniformPrior
 from .patches import GaussianMixtureModel, GMMPatchPrior
 
 PRIOR_REGISTRY = {
@@ -6,6 +6,7 @@ PRIOR_REGISTRY = {
     "gmm-patches": GMMPatchPrior,
     "inverse-gamma": InverseGammaPrior,
     "exponential": ExponentialPrior,
+    "smooth": SmoothnessPrior,
 }
 
 __all__ = [
@@ -14,6 +15,7 @@ __all__ = [
     "ExponentialPrior",
     "UniformPrior",
     "InverseGammaPrior",
+    "SmoothnessPrior",
     "Prior",
     "Priors",
     "PRIOR_REGISTRY",

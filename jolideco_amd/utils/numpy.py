@@ -13,6 +13,7 @@ __all__ = [
     "reconstruct_from_overlapping_patches",
     "split_datasets_validation",
     "next_fast_len_2357",
+    "gaussian_kernel_2d",
 ]
 
 
@@ -111,3 +112,20 @@ def next_fast_len_2357(n, multiple=1):
         if r == 1:
             return m
         m += multiple
+
+
+def gaussian_kernel_2d(width):
+    """Square float64 array of a 2-D Gaussian of standard deviation ``width`` pixels, sampled at the pixel centres, on an
+    odd number of pixels >= 8 * width (17 for width 2), normalised to sum 1: the array of astropy's
+    ``Gaussian2DKernel(width)`` (>= 5.2), which the reference's SmoothnessPrior convolves with (priors/core.py:376-380)."""
+    sigma = float(width)
+    if not sigma > 0:
+        raise ValueError(f"width must be positive, got {width!r}")
+    size = int(np.ceil(8 * sigma))
+    if size % 2 == 0:
+        size += 1
+    axis = np.arange(-(size - 1) // 2, (size - 1) // 2 + 1, dtype=float)
+    x, y = np.meshgrid(axis, axis)
+    amplitude = 1.0 / (2 * np.pi * sigma**2)
+    array = amplitude * np.exp(-0.5 * (x**2 + y**2) / sigma**2)
+    return array / array.sum()

@@ -8,6 +8,9 @@ __all__ = [
     "convolve_fft_torch",
     "cycle_spin_shifts",
     "cycle_spin",
+    "subpixel_offsets",
+    "subpixel_offsets_many",
+    "subpixel_kernel",
     "get_default_generator",
     "view_as_overlapping_patches_torch",
 ]
@@ -57,6 +60,40 @@ def cycle_spin_shifts_many(patch_shape, generator, n):
         return [cycle_spin_shifts(patch_shape, generator) for _ in range(n)]
     values = torch.randint(-wy, wy + 1, (2 * n,), generator=generator).tolist()
     return [(values[2 * i], values[2 * i + 1]) for i in range(n)]
+
+
+def subpixel_offsets(generator):
+    """The offsets (x0, y0) of one sub-pixel cycle spin, drawn exactly like jolideco/utils/torch.py:139-140: two float32
+    `rand(1) - 0.5` draws from a HOST generator, x first.  Returned as Python floats (exact images of the float32 values)."""
+    x0 = torch.rand(1, generator=generator) - 0.5
+    y0 = torch.rand(1, generator=generator) - 0.5
+    return float(x0), float(y0)
+
+
+def subpixel_offsets_many(generator, n):
+    """`n` consecutive draws of `subpixel_offsets` in one `rand` call: the CPU generator hands out one float32 per element
+    in order, so `rand(2 n)` returns the numbers of 2 n single draws and leaves the generator in the same state
+    (tests/test_priors_golden.py holds torch to that, for every size up to the limit used here)."""
+    if n < 1 or 2 * n > SUBPIX_BATCH_MAX:
+        return [subpixel_offsets(generator) for _ in range(n)]
+    values = (torch.rand(2 * n, generator=generator) - 0.5).tolist()
+    return [(values[2 * i], values[2 * i + 1]) for i in range(n)]
+
+
+SUBPIX_BATCH_MAX = 1024  # numbers per `rand` call (an epoch of 511 datasets); more are drawn pair by pair
+
+
+def subpixel_kernel(x0, y0):
+    """(3, 3) float32 stencil of `grid_weights` (jolideco/utils/torch.py:31-38) for the offsets (x0, y0):
+    k[i][j] = wx(j - 1) wy(i - 1), w(t) = 1 - |t - o| where |t - o| < 1, else 0, in float32 operations."""
+    grid = torch.arange(-1, 2)
+    y, x = torch.meshgrid(grid, grid, indexing="ij")
+    x0, y0 = torch.tensor([x0], dtype=torch.float32), torch.tensor([y0], dtype=torch.float32)
+    dx = torch.abs(x - x0)
+    dx = torch.where(dx < 1, 1 - dx, 0)
+    dy = torch.abs(y - y0)
+    dy = torch.where(dy < 1, 1 - dy, 0)
+    return dx * dy
 
 
 def cycle_spin(image, patch_shape, generator):
