@@ -106,6 +106,18 @@ int jd_conv_native_fft_supported(int H, int W, int kh, int kw);
  * width a multiple of 4, enough pixels x datasets to fill the chip; option JD_SEP_WALK = 0 / 1 forces either).  Both
  * compute the same function; a benchmark uses this to name the kernel it timed. */
 int jd_conv_plan_takes_walk(const jd_conv_plan* plan, int n_datasets);
+/* Which kernels a likelihood step of `n_datasets` datasets (1 = the per-dataset call) with up-sampling factor `upsampling`
+ * launches on this plan -- asked of the functions the launch path itself asks; read-only, no device work.  A test uses it
+ * to pin a case to the kernel it means to check.  route8 =
+ *   [0], [1]  Nx, Ny: lengths of the native row / column transforms (0: not a native FFT plan)
+ *   [2], [3]  row schedule of the forward-row launch and of the pooled middle launch: 0 generic-large, 1 2304, 2 4608,
+ *             3 1152, 4 generic-small, 5 one-wave tiny; -1: no such launch
+ *   [4]       1 when the fused up-sampled (pooled) launches take this factor and grid
+ *   [5]       1 when the column passes exchange pooled row groups with the middle launch
+ *   [6]       jd_npred_poisson_calibrated_batch_fwd_bwd: 0 per-dataset calls, 1 every launch over all datasets,
+ *             2 the FFT launches dataset by dataset and the tail over all
+ *   [7]       transposed shift: R = 1, 2, 4 rows per thread of the four-pixel kernel (16-byte aligned images), 0 scalar kernels */
+int jd_conv_plan_step_route(const jd_conv_plan* plan, int upsampling, int n_datasets, int32_t* route8);
 /* The frame -- 17 or 33 taps per direction -- in which the strip-walk kernels run the operator `khat` that
  * jd_conv_psf_spectrum built for this SEPARABLE plan, or 0 when they do not take it (rank > 1, non-zero taps wider than 33,
  * a buffer the library did not build).  The frame follows from the NON-ZERO taps of the operator, not from the plan's

@@ -852,6 +852,29 @@ extern "C" int jd_npred_poisson_batch_fwd_bwd(jd_conv_plan* p, int n_datasets, c
                                               eps, loss_out, grad_flux ? grads : nullptr, accumulate, grad_scale, stream);
 }
 
+// How jd_npred_poisson_calibrated_batch_fwd_bwd runs `n_datasets` datasets (the measurements are in its body): 0 = the
+// per-dataset calls, 1 = every launch over all datasets, 2 = the FFT launches dataset by dataset and the tail over all.
+static int calibrated_batch_form(const jd_conv_plan* p, int n_datasets, int upsampling, bool with_grad) {
+  const int mode = opt_value(OPT_FFT_BATCH, 1);
+  const bool batched = p->native && with_grad && n_datasets >= 2 && n_datasets <= FFT_MAX_BATCH &&
+                       fftn_pooled_supported(p->fftn, upsampling) && !opt_is_set(OPT_SEP_NO_FUSION) && mode != 0 &&
+                       (p->fftn.Hh <= 1024 || mode != 3);
+  return !batched ? 0 : p->fftn.Hh > 1024 && mode == 4 ? 2 : 1;
+}
+
+extern "C" int jd_conv_plan_step_route(const jd_conv_plan* p, int upsampling, int n_datasets, int32_t* route8) {
+  JD_REQUIRE(p && route8, "jd_conv_plan_step_route: null argument");
+  JD_REQUIRE(upsampling >= 1 && upsampling <= 8 && n_datasets >= 1, "jd_conv_plan_step_route: upsampling = %d, n_datasets = %d",
+             upsampling, n_datasets);
+  const int form = calibrated_batch_form(p, n_datasets, upsampling, true);
+  int fft[6] = {0, 0, -1, -1, 0, 0};
+  if (p->native) fftn_step_route(p->fftn, upsampling, form == 1 ? n_datasets : 1, fft);
+  for (int i = 0; i < 6; ++i) route8[i] = fft[i];
+  route8[6] = form;
+  route8[7] = shift_bwd_route(p->H, p->W);
+  return JD_OK;
+}
+
 // The joint step over several CALIBRATED and / or UP-SAMPLED datasets of one flux component on the native FFT path
 // (include/jolideco_hip.h).  Anything else -- another method, an up-sampling factor the fused launches do not take, a
 // forward-only evaluation, switched-off fusion -- runs the per-dataset calls this stands for.
@@ -879,11 +902,8 @@ extern "C" int jd_npred_poisson_calibrated_batch_fwd_bwd(jd_conv_plan* p, int n_
   // only the tail over all datasets 4.63 (the tail alone: 383 us against 8 x 54).  So: every launch over all datasets, at
   // every size (JD_FFT_BATCH = 0: per-dataset calls; 3: per-dataset calls beyond 2048 rows, the round-4 rule; 4: beyond
   // 2048 rows the FFT launches dataset by dataset, the tail over all datasets).
-  const int mode = opt_value(OPT_FFT_BATCH, 1);
-  const bool batched = p->native && grad_flux && n_datasets >= 2 && n_datasets <= FFT_MAX_BATCH &&
-                       fftn_pooled_supported(p->fftn, upsampling) && !opt_is_set(OPT_SEP_NO_FUSION) && mode != 0 &&
-                       (p->fftn.Hh <= 1024 || mode != 3);
-  const bool sequential = batched && p->fftn.Hh > 1024 && mode == 4;
+  const int form = calibrated_batch_form(p, n_datasets, upsampling, grad_flux != nullptr);
+  const bool batched = form != 0, sequential = form == 2;
   if (!batched) {
     const float* fluxes[1] = {flux};
     float* grads[1] = {grad_flux};

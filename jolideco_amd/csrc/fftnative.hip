@@ -1578,4 +1578,17 @@ int fftn_poisson_step_pooled_batch(const FftNative& n, int upsampling, int nd, c
   return any ? launch_finalize_multi_batch(partials_shift, shift_stride, shift_blocks, nd, shift_out, stream) : JD_OK;
 }
 
+// The kernels the up-sampled likelihood step launches for `per_launch` datasets per launch (jd_conv_plan_step_route):
+// route6 = {Nx, Ny, row schedule of the forward-row launch, of the pooled launch (-1: none), fftn_pooled_supported,
+// pooled column I/O} -- asked of the functions the launches above ask.
+void fftn_step_route(const FftNative& n, int upsampling, int per_launch, int* route6) {
+  const FftPasses f = passes_of(n.Nx);
+  const bool pooled = fftn_pooled_supported(n, upsampling);
+  route6[0] = n.Nx, route6[1] = n.Ny;
+  route6[2] = row_schedule(f, n.Nx, n.W, n.Hh * per_launch);
+  route6[3] = pooled ? row_schedule(f, n.Nx, n.W, n.Hh / upsampling * per_launch) : -1;
+  route6[4] = pooled ? 1 : 0;
+  route6[5] = pooled && pooled_column_io(n, upsampling) > 1 ? 1 : 0;
+}
+
 }  // namespace jd

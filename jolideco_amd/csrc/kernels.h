@@ -56,6 +56,7 @@ int launch_shift_fwd(const float* in, float* out, int H, int W, const float* shi
 int launch_shift_bwd(const float* in, const float* gs, float* grad_in, int accumulate, int H, int W,
                      const float* shift_xy, float scale, double* partials, int* n_blocks, hipStream_t stream);
 int shift_bwd_max_blocks(int H, int W);
+int shift_bwd_route(int H, int W);  // R (1, 2, 4) of the four-pixel backward kernel an aligned H x W image takes, 0: scalar kernels
 // out[i] = [out[i] +] scale * sum_b partials[n_out * b + i]   (i < n_out; one fixed-order pass)
 // grad_in (+)= sum_d shift_d^T(gs_d) in dataset order (datasets without a shift: + gs_d), and per dataset the partial sums of
 // d loss / d shift_xy; batch (device memory): gshift, shift_xy per dataset
@@ -285,6 +286,7 @@ int fftn_poisson_step_pooled_batch(const FftNative& n, int upsampling, int nd, c
                                    double* partials_shift, float coef, int accumulate, hipStream_t stream, double loss_scale,
                                    double norm_grad_scale, int sequential);
 bool fftn_pooled_supported(const FftNative& n, int upsampling);
+void fftn_step_route(const FftNative& n, int upsampling, int per_launch, int* route6);
 int fftn_poisson_step_pooled(const FftNative& n, int upsampling, const float* flux, const float* exposure, const float2* khat,
                              const float* background, const float* counts, const float* log_bkg_norm, double* partials,
                              double* partials_b, float eps, float inv_n, float* target, float coef, int accumulate,

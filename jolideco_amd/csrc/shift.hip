@@ -300,6 +300,10 @@ static bool shift_vec_ok(const void* a, const void* b, const void* c, int W) {
   return W % 4 == 0 && W >= 8 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
+int shift_bwd_route(int H, int W) {  // R of the four-pixel kernel, 0: the scalar kernels (aligned images assumed)
+  return shift_vec_ok(nullptr, nullptr, nullptr, W) ? shift_tiling(H, W).R : 0;
+}
+
 int launch_shift_bwd_batch(const float* in, const FftBatch* batch, int n_datasets, float* grad_in, int accumulate, int H, int W,
                            float scale, double* partials, size_t partials_stride, int* n_blocks, hipStream_t stream) {
   // (the batch table's images are hipMalloc'ed by the plan: 256-byte aligned)

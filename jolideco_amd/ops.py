@@ -152,6 +152,22 @@ class ConvPlan:
         """True when a launch over ``n_datasets`` datasets runs on the strip-walk kernels (jd_conv_plan_takes_walk)."""
         return bool(_hip.lib().jd_conv_plan_takes_walk(self._handle, int(n_datasets)))
 
+    ROW_SCHEDULES = ("generic-large", "2304", "4608", "1152", "generic-small", "tiny")  # row_schedule of csrc/fftnative.hip
+
+    def step_route(self, upsampling=1, n_datasets=1):
+        """The kernels a likelihood step of ``n_datasets`` datasets with this up-sampling factor launches
+        (jd_conv_plan_step_route): dict of ``Nx``, ``Ny``, ``rows_fwd`` / ``rows_pooled`` (a name of `ROW_SCHEDULES` or None),
+        ``pooled_supported``, ``pooled_column_io``, ``batched`` (0 per-dataset calls, 1 launches over all datasets, 2 FFT
+        launches per dataset with a common tail) and ``shift_bwd_rows`` (R of the four-pixel kernel, 0: scalar kernels)."""
+        out = (ctypes.c_int32 * 8)()
+        check(_hip.lib().jd_conv_plan_step_route(self._handle, int(upsampling), int(n_datasets), out))
+        name = lambda i: self.ROW_SCHEDULES[i] if i >= 0 else None  # noqa: E731
+        return {
+            "Nx": int(out[0]), "Ny": int(out[1]), "rows_fwd": name(out[2]), "rows_pooled": name(out[3]),
+            "pooled_supported": bool(out[4]), "pooled_column_io": bool(out[5]), "batched": int(out[6]),
+            "shift_bwd_rows": int(out[7]),
+        }
+
     # --- kernel spectrum (once per dataset and component) -----------------------------------
     def psf_spectrum(self, psf, out=None):
         """The kernel operator of `psf` for this plan (jd_conv_psf_spectrum).  Operator buffers are immutable: to change

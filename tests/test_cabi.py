@@ -70,6 +70,9 @@ def test_argument_validation_reports_errors(lib):
     assert lib.jd_adam_step(None, None, None, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, None, None) == -1
     assert lib.jd_elementwise_prior_fwd_bwd(7, None, 0, 0, 0, 0, None, 0, None, None) == -1
     assert lib.jd_profile_enable(0) == -1
+    route = (ctypes.c_int32 * 8)()
+    assert lib.jd_conv_plan_step_route(None, 2, 1, route) == -1
+    assert b"null argument" in lib.jd_last_error()
     total, count = ctypes.c_double(), ctypes.c_longlong()
     assert lib.jd_profile_read(99, ctypes.byref(total), ctypes.byref(count)) == -1
     # destroying a null handle is a no-op
