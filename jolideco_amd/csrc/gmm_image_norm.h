@@ -1,4 +1,4 @@
-// Image norms of the GMM patch prior, shared by the 8x8 (gmm.hip) and the 16x16 (gmm256.hip) kernels: n(f), n'(f), the
+// Image norms of the GMM patch prior, shared by the 8x8 (gmm_gather.hip) and the 16x16 (gmm256.hip) kernels: n(f), n'(f), the
 // argument block of the overlap-add kernels and the chain-rule term they add.  ONE definition of each, so both patch
 // sizes produce the same bits for the same pixel.
 #pragma once

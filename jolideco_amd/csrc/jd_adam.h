@@ -1,5 +1,5 @@
 // The optimizer update of one pixel, shared by the stand-alone kernel (elementwise.hip: adam_kernel) and by the gather
-// kernel of the GMM prior that applies it in its epilogue (gmm.hip): ONE device function, so both produce the same bits.
+// kernel of the GMM prior that applies it in its epilogue (gmm_gather.hip): ONE device function, so both produce the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 

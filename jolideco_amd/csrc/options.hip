@@ -23,10 +23,10 @@ OptionSlot g_options[OPT_COUNT] = {
     {"JD_SEP_WALK_COLS", {INT_MIN}},     {"JD_SEP_WALK_ROWS", {INT_MIN}},    {"JD_SEP_WALK_ADJ_COLS", {INT_MIN}},
     {"JD_SEP_WALK_ADJ_ROWS", {INT_MIN}}, {"JD_DIRECT_FP32", {INT_MIN}},      {"JD_CONV_BLOCKS_PER_CU", {INT_MIN}},
     {"JD_POISSON_ROWS", {INT_MIN}},      {"JD_GMM_NO_HOST_STATS", {INT_MIN}}, {"JD_GMM_BLOCK_TILES", {INT_MIN}},
-    {"JD_GMM_DENSE", {INT_MIN}},         {"JD_GMM_KSPLIT", {INT_MIN}},       {"JD_GMM_SCREEN_NP", {INT_MIN}},
+    {"JD_GMM_DENSE", {INT_MIN}},         {"JD_GMM_KSPLIT", {INT_MIN}},
     {"JD_GMM_SCREEN_NO_LDS_CONSTS", {INT_MIN}}, {"JD_GMM_SCREEN_DEBUG", {INT_MIN}}, {"JD_GMM_SCREEN", {INT_MIN}},
     {"JD_GMM_FUSED_BWD", {INT_MIN}},     {"JD_GMM_GATHER_TILED", {INT_MIN}}, {"JD_GMM_LSE_SCREEN", {INT_MIN}},
-    {"JD_GMM_WINNER_ROWS", {INT_MIN}},   {"JD_SEP_JOINT", {INT_MIN}},        {"JD_SEP_JOINT_ROWS", {INT_MIN}},
+    {"JD_SEP_JOINT", {INT_MIN}},         {"JD_SEP_JOINT_ROWS", {INT_MIN}},
     {"JD_SEP_JOINT_CHUNK", {INT_MIN}},   {"JD_SEP_WALK_ADJ_ALL", {INT_MIN}}, {"JD_SEP_WALK_COST33", {INT_MIN}},
     {"JD_SEP_WALK_ROWS33", {INT_MIN}},   {"JD_SEP_NO_TRIM", {INT_MIN}},      {"JD_SEP_WALK_ADJ_ROWS33", {INT_MIN}},
     {"JD_SEP_WALK_ADJ33", {INT_MIN}},    {"JD_FFT_NATIVE", {INT_MIN}},

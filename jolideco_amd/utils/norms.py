@@ -2,7 +2,7 @@
 
 Image norms (reference jolideco/utils/norms.py:225-426): identity, asinh, fixed-max, sigmoid, atan, log and power.  On
 the device the norm is one streaming pass in front of the patch kernels and its derivative rides in the gather kernel
-(csrc/gmm.hip); the classes here carry the parameters, the plain-torch evaluation (any device) and the (de)serialisation.
+(csrc/gmm_gather.hip); the classes here carry the parameters, the plain-torch evaluation (any device) and the (de)serialisation.
 ``"max"`` (a global reduction) and ``"inverse-cdf"`` (a table lookup) are not implemented and raise NotImplementedError.
 Patch norms: `SubtractMeanPatchNorm` (:97-103, fused into the HIP kernel).
 """
@@ -47,7 +47,7 @@ class PatchNorm:
 
 class SubtractMeanPatchNorm(PatchNorm):
     """Subtract the patch mean (Zoran & Weiss).  On device this is fused into the GMM kernel
-    (csrc/gmm.hip); this host version works on torch tensors for explicit patch arrays."""
+    (csrc/gmm_gather.hip); this host version works on torch tensors for explicit patch arrays."""
 
     def __call__(self, patches):
         return patches - patches.nanmean(dim=1, keepdim=True)

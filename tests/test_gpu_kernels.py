@@ -559,12 +559,15 @@ def test_gmm_logsumexp_screen_equals_the_dense_kernels(jd_option):
     means, covs, weights = synthetic_gmm(24, 64, seed=9)
     handle = GaussianMixtureModel.from_numpy(means, covs, weights, meta=GaussianMixtureModelMeta(stride=4)).handle(DEV)
     half = np.where(xx < shape[1] // 2, smooth, noisy).astype(np.float32)
-    for image in (noisy, smooth, half):
-        for rows in ((0, -1), (5, 19)):
-            for _ in range(3):  # (the record buffer of a handle grows over the first passes: all of them must be right)
-                a, b = run(handle, image, True, rows), run(handle, image, False, rows)
-                np.testing.assert_allclose(a[0], b[0], rtol=2e-6)
-                assert rel_linf(a[1], b[1]) < 5e-5 and np.abs(b[1]).max() > 0
+    for ksplit in (None, 0, 1):  # the decomposition the launch picks, then either one forced
+        jd_option("JD_GMM_KSPLIT", ksplit)
+        for image in (noisy, smooth, half):
+            for rows in ((0, -1), (5, 19)):
+                for _ in range(3):  # (the record buffer of a handle grows over the first passes: all of them must be right)
+                    a, b = run(handle, image, True, rows), run(handle, image, False, rows)
+                    np.testing.assert_allclose(a[0], b[0], rtol=2e-6)
+                    assert rel_linf(a[1], b[1]) < 5e-5 and np.abs(b[1]).max() > 0
+    jd_option("JD_GMM_KSPLIT", None)
     # fallbacks on the device: the gated dense kernels take the pass -> the same bits as the dense path
     means, covs, weights = synthetic_gmm(1, 64, seed=3)
     gmm40 = GaussianMixtureModel.from_numpy(np.repeat(means, 40, axis=0), np.repeat(covs, 40, axis=0), np.full(40, 1 / 40),
@@ -621,7 +624,7 @@ def test_marginalized_prior_fit_matches_oracle():
      ((200, 168), 64, 4, 0.02), ((120, 136), 16, 5, 1.0)],
 )
 def test_gmm_screened_argmax_is_bit_identical_to_dense(shape, K, seed, mean_scale, jd_option):
-    """Max mode through the bf16 screen + exact fp32 re-evaluation of the survivors (csrc/gmm.hip, gmm_screen_kernel)
+    """Max mode through the bf16 screen + exact fp32 re-evaluation of the survivors (csrc/gmm_screen.hip, gmm_screen_kernel)
     returns exactly the dense fp32 kernel's numbers: same arg-max for every patch, same value bits, same gradient
     bits -- on noise, on smooth structure with bright points, with filtered patches and with cycle-spin shifts; also
     for mixtures with small (trained-GMM like) and large component means, which only widen the screen's bounds."""
@@ -643,20 +646,49 @@ def test_gmm_screened_argmax_is_bit_identical_to_dense(shape, K, seed, mean_scal
     images["noise"][5:9, 7:11] = -2e5  # filtered patches (patches/core.py:215)
     handle = gmm.handle(DEV)
     n_patches = ((shape[0] - 8) // 4 + 1) * ((shape[1] - 8) // 4 + 1)
+
+    def run(h, flux, shifts, **switches):
+        for key, value in switches.items():
+            jd_option(key, value)
+        value, grad = torch.zeros(1, device=DEV), torch.zeros_like(flux)
+        argmax = torch.full((n_patches,), -7, dtype=torch.int32, device=DEV)
+        h.prior_fwd_bwd(flux, 4, shifts, value, 0.25, grad=grad, grad_coef=0.5, argmax_out=argmax)
+        torch.cuda.synchronize()
+        for key in switches:
+            jd_option(key, None)
+        return float(value), grad.cpu().numpy(), argmax.cpu().numpy()
+
+    # launch variants of the screened path (and, with the screen off, of the dense kernel): the default everywhere; at the
+    # smallest case also both decompositions of the screen with its constants in LDS and in global memory, sort kernels
+    # that stride over the record segments, and every block size of the dense kernel
+    variants = [dict(JD_GMM_SCREEN=1)]
+    if shape == (96, 128):
+        variants += [dict(JD_GMM_SCREEN=1, JD_GMM_KSPLIT=ks, JD_GMM_SCREEN_NO_LDS_CONSTS=no_lds) for ks in (0, 1) for no_lds in (None, 1)]
+        variants += [dict(JD_GMM_SCREEN=1, JD_GMM_SORT_BLOCKS=b) for b in (1, 3)]
+        variants += [dict(JD_GMM_SCREEN=0, JD_GMM_BLOCK_TILES=tb) for tb in (4, 8, 16)]
+
+    def same(got, ref, what):
+        assert np.array_equal(got[2], ref[2]), what
+        assert got[0] == ref[0] or abs(got[0] - ref[0]) <= 2e-7 * abs(ref[0]), what
+        assert np.array_equal(got[1], ref[1]), what
+
+    dense = {}
     for name, image in images.items():
         flux = torch.from_numpy(image.astype(np.float32)).to(DEV)
         for shifts in [(0, 0), (-2, 1)]:
-            out = {}
-            for mode in ("1", "0"):
-                jd_option("JD_GMM_SCREEN", mode)
-                value, grad = torch.zeros(1, device=DEV), torch.zeros_like(flux)
-                argmax = torch.full((n_patches,), -7, dtype=torch.int32, device=DEV)
-                handle.prior_fwd_bwd(flux, 4, shifts, value, 0.25, grad=grad, grad_coef=0.5, argmax_out=argmax)
-                torch.cuda.synchronize()
-                out[mode] = (float(value), grad.cpu().numpy(), argmax.cpu().numpy())
-            assert np.array_equal(out["1"][2], out["0"][2]), (name, shifts)
-            assert out["1"][0] == out["0"][0] or abs(out["1"][0] - out["0"][0]) <= 2e-7 * abs(out["0"][0]), (name, shifts)
-            assert np.array_equal(out["1"][1], out["0"][1]), (name, shifts)
+            dense[name, shifts] = run(handle, flux, shifts, JD_GMM_SCREEN=0)
+            for switches in variants:
+                same(run(handle, flux, shifts, **switches), dense[name, shifts], (name, shifts, switches))
+    if shape == (96, 128):
+        # the stamped instantiation of the default screen (jd_gmm_screen_clock; the armed state sticks to a handle: a
+        # freshly built mixture)
+        armed = GaussianMixtureModel.from_numpy(means, covs, weights, meta=GaussianMixtureModelMeta(stride=4)).handle(DEV)
+        armed.screen_clock()
+        for name, image in images.items():
+            flux = torch.from_numpy(image.astype(np.float32)).to(DEV)
+            for shifts in [(0, 0), (-2, 1)]:
+                same(run(armed, flux, shifts, JD_GMM_SCREEN=1, JD_GMM_KSPLIT=0), dense[name, shifts], (name, shifts, "clock"))
+        assert armed.screen_clock()[1] > 0
     # a patch-row shard (multi-GPU partition) goes through the same path
     flux = torch.from_numpy(images["noise"].astype(np.float32)).to(DEV)
     rows = (shape[0] - 8) // 4 + 1
