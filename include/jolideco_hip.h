@@ -496,6 +496,37 @@ int jd_adam_step_multi(int n_tensors, float* const* theta, const float* const* g
 int jd_sgd_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
                 const float* mask, size_t n, float lr, int zero_grad, int use_log_flux, void* stream);
 
+/* Sparse point-source flux component (models/core.py:54-342, utils/torch.py:31-38) ------------------------------
+ * A list of n sources: param_flux[i] = log(flux_i) when use_log_flux != 0, else flux_i; x_pos[i] / y_pos[i] pixel
+ * coordinates (pixel centres at integers, x indexes columns, y rows -- the reference's component compares its `x_pos` with
+ * the ROW index, models/core.py:198-223, so the Python layer passes its `y_pos` as x_pos here and its `x_pos` as y_pos).
+ * All vectors: device, n floats.
+ *
+ * jd_sparse_render: flux_out (H, W) <- the rendered image.  EVERY pixel is written:
+ *   flux_out[y, x] = sum_i (wx_i(x) * wy_i(y)) * f_i,   w(t) = 1 - |t - t0| where |t - t0| < 1, else 0,
+ *   f_i = exp(param_flux[i]) or param_flux[i],
+ * the weights in the reference's float32 operations one by one (no contraction), the sum over the sources that touch the
+ * pixel in ascending index order, 0 where none does.  A source touches at most 2 x 2 pixels; one on an exactly integer
+ * coordinate touches one column (row); one whose taps all lie outside the image contributes nothing.  Two launches (the
+ * zero fill; one thread per (source, tap): the thread of the lowest source index on a pixel sums and stores it), no
+ * atomics: run-to-run identical however many sources share a pixel.  Every tap is tested against every source:
+ * O(n^2) work, for the hundreds to thousands of sources such a component holds.
+ * Supported: 1 <= n <= jd_sparse_max_sources() (65536), 1 <= H, W <= 2^24; JD_ERR_INVALID beyond, and for null pointers. */
+int jd_sparse_max_sources(void);
+int jd_sparse_render(const float* param_flux, const float* x_pos, const float* y_pos, int n, int use_log_flux, int H,
+                     int W, float* flux_out, void* stream);
+/* The gradients of a loss with respect to the three vectors, given grad_flux_image = d loss / d flux_out (H, W): one
+ * thread per source reads its <= 4 taps G and ASSIGNS (nothing is accumulated)
+ *   grad_param[i] = c_i * sum wx wy G               (c_i = f_i for log flux, 1 for linear flux)
+ *   grad_x[i]     = f_i * sum sign(x - x_i) wy G
+ *   grad_y[i]     = f_i * sum wx sign(y - y_i) G
+ * with sign(0) = 0, as torch.abs / torch.where differentiate: a source on an exactly integer coordinate gets an exactly
+ * zero position gradient on that axis.  Taps outside the image are skipped; a source wholly outside gets three zeros.
+ * Same limits as jd_sparse_render. */
+int jd_sparse_backward(const float* param_flux, const float* x_pos, const float* y_pos, int n, int use_log_flux, int H,
+                       int W, const float* grad_flux_image, float* grad_param, float* grad_x, float* grad_y,
+                       void* stream);
+
 /* Kernel timers -----------------------------------------------------------------------------
  * New (the reference has no profiler hooks).  After jd_profile_enable(n) the
  * library brackets every launch of the kernels below with a hipEvent pair on the launch stream
@@ -524,7 +555,9 @@ enum {
   JD_KERNEL_ELEMENTWISE_SUBPIX = 18, /* element-wise priors with sub-pixel cycle spin: stencil + value + adjoint stencil */
   JD_KERNEL_SMOOTHNESS = 19,     /* smoothness prior: sum f (K * f) and its gradient behind the convolution */
   JD_KERNEL_ELEMENTWISE_PRIOR = 20, /* element-wise priors (inverse-gamma, exponential): value + gradient */
-  JD_KERNEL_COUNT = 21
+  JD_KERNEL_SPARSE_RENDER = 21,  /* sparse component: zero fill + one thread per (source, tap), index-ordered sums */
+  JD_KERNEL_SPARSE_BACKWARD = 22, /* sparse component: gradients of flux and positions from the <= 4 taps of a source */
+  JD_KERNEL_COUNT = 23
 };
 int jd_profile_enable(int capacity);
 int jd_profile_disable(void);

@@ -11,6 +11,7 @@ from .models import (
     NPredCalibrations,
     NPredModel,
     NPredModels,
+    SparseSpatialFluxComponent,
     SpatialFluxComponent,
 )
 from .priors import (
@@ -33,6 +34,7 @@ __all__ = [
     "TotalLoss",
     "FluxComponents",
     "SpatialFluxComponent",
+    "SparseSpatialFluxComponent",
     "NPredModel",
     "NPredModels",
     "NPredCalibration",

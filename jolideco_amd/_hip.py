@@ -127,6 +127,11 @@ EXPORTS = {
         [c_int, fpp, fpp, fpp, fpp, POINTER(c_int), fp, fp, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p],
     ),
     "jd_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_int, c_int, c_void_p]),
+    "jd_sparse_max_sources": (c_int, []),
+    "jd_sparse_render": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "jd_sparse_backward": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "jd_profile_enable": (c_int, [c_int]),
     "jd_profile_disable": (c_int, []),
     "jd_profile_pause": (c_int, [c_int]),
@@ -158,6 +163,7 @@ KERNEL_IDS = {
     "adjoint_epilogue": 6, "adam": 7, "fft_r2c": 8, "fft_c2r": 9, "direct_conv": 10, "sep_conv": 11,
     "gmm_screen": 12, "gmm_sort": 13, "gmm_exact": 14, "gmm_stage": 15, "shift": 16,
     "poisson_mixed": 17, "elementwise_subpix": 18, "smoothness": 19, "elementwise_prior": 20,
+    "sparse_render": 21, "sparse_backward": 22,
 }
 
 _lib = None

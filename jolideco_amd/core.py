@@ -28,8 +28,8 @@ from . import _hip
 from ._hip import check, ptr, ptr_array, stream_ptr
 from .distributed import DistContext
 from .loss import TotalLoss
-from .models import FluxComponents, SpatialFluxComponent
-from .ops import adam_bias_terms
+from .models import FluxComponents, SparseSpatialFluxComponent, SpatialFluxComponent
+from .ops import adam_bias_terms, sparse_backward, sparse_render
 from .utils.torch import TORCH_DEFAULT_DEVICE
 
 log = logging.getLogger(__name__)
@@ -85,6 +85,56 @@ class _ComponentState:
     @property
     def flux_prev(self):
         return self.flux[1 - self.cur]
+
+
+class _SparseComponentState:
+    """Device buffers of a `SparseSpatialFluxComponent` during a fit.  To the likelihood, the priors and the trace it is a
+    dense component: two flux buffers that hold RENDERED images, and its slice of the flat gradient buffer, the gradient
+    with respect to that image.  The parameters are the three source vectors (the nn.Parameters' storage); their
+    gradients live in persistent vectors, and a stepper of the calibration kind applies the optimizer to them."""
+
+    is_sparse = True
+
+    def __init__(self, name, component, grad, deconvolver):
+        self.name = name
+        self.component = component
+        self.params = [component._flux, component.x_pos, component.y_pos]
+        # the kernels' argument order (flux, column coordinate, row coordinate): `y_pos` runs along the columns
+        # (SparseSpatialFluxComponent)
+        self._kernel_order = [component._flux, component.y_pos, component.x_pos]
+        if not all(p.is_cuda for p in self.params):
+            raise RuntimeError("components must be on a HIP device: jolideco_amd has no CPU path")
+        self.shape = tuple(component.shape[-2:])
+        self.mask = None
+        device = self.params[0].device
+        self.flux = [torch.empty(self.shape, dtype=torch.float32, device=device) for _ in range(2)]
+        self.cur = 0
+        self.grad = grad.reshape(self.shape)  # view into the flat communication buffer: d loss / d image
+        self.frozen = component.frozen
+        self.use_log_flux = bool(component.use_log_flux)
+        # (`flux` is rendered anew on every access: the trace sees the image of the last step, models/core.py:216-232)
+        self.trace_sees_current = False
+        for p in self.params:
+            p.grad = torch.zeros_like(p.data)
+        self.stepper = _CalibrationStepper(self.params, deconvolver)
+        self.render(self.flux[0])
+
+    def render(self, out):
+        sparse_render(*(p.data for p in self._kernel_order), self.use_log_flux, out)
+
+    def step(self, step):
+        """The optimizer step number ``step`` of the three vectors from the image gradient: backward, the stepper,
+        render into the other flux buffer (the caller swaps)."""
+        order = self._kernel_order
+        sparse_backward(*(p.data for p in order), self.use_log_flux, self.grad, *(p.grad for p in order))
+        for state in self.stepper.state:
+            state["step"] = step - 1  # (the session's count: the stepper adds one)
+        self.stepper.step()
+        self.render(self.flux[1 - self.cur])
+
+    flux_trace = _ComponentState.flux_trace
+    flux_cur = _ComponentState.flux_cur
+    flux_prev = _ComponentState.flux_prev
 
 
 class MAPDeconvolver:
@@ -207,13 +257,16 @@ class MAPDeconvolver:
         lib = _hip.lib()
         lr = self.optimizer_kwargs["lr"]
         for ci, st in enumerate(states):
-            n = st.theta.numel()
-            stream = stream_ptr(st.theta.device)
+            n = st.grad.numel()
+            stream = stream_ptr(st.grad.device)
             if ci in stepped:
                 pass
             elif st.frozen:
                 st.flux[1 - st.cur].copy_(st.flux_cur)
                 st.grad.zero_()
+            elif getattr(st, "is_sparse", False):
+                # backward to the source vectors, their optimizer step, the image of the new sources
+                st.step(step)
             elif self.optimizer_type == "adam":
                 beta1, beta2 = self.optimizer_kwargs.get("betas", (0.9, 0.999))
                 eps = self.optimizer_kwargs.get("eps", 1e-8)
@@ -235,6 +288,17 @@ class MAPDeconvolver:
                 )
             st.cur = 1 - st.cur
 
+    def _as_components(self, components):
+        if isinstance(components, SparseSpatialFluxComponent):
+            # (the reference fails here too, inside `FluxComponents(component)`: jolideco/core.py:190-193)
+            raise TypeError(
+                "a bare SparseSpatialFluxComponent cannot be fitted: put it in a FluxComponents, e.g. "
+                "FluxComponents({'points': component})"
+            )
+        if isinstance(components, SpatialFluxComponent):
+            components = {self._default_flux_component: components}
+        return FluxComponents(components)
+
     def run(self, datasets, datasets_validation=None, components=None, calibrations=None):
         """Run the MAP deconvolver
 
@@ -255,9 +319,7 @@ class MAPDeconvolver:
         """
         if self.stop_early and datasets_validation is None:
             raise ValueError("Early stopping requires providing test datasets")
-        if isinstance(components, SpatialFluxComponent):
-            components = {self._default_flux_component: components}
-        components = FluxComponents(components)
+        components = self._as_components(components)
         components_init = copy.deepcopy(components)
         calibrations_init = copy.deepcopy(calibrations) if calibrations is not None else None
 
@@ -271,9 +333,7 @@ class MAPDeconvolver:
         """Set up a fit without running it: uploads the datasets, builds the FFT plans / kernel
         spectra / GMM handles and returns a `FitSession` whose ``epoch()`` enqueues one epoch of
         the fit on the current HIP stream (used by `run` and by bench.py)."""
-        if isinstance(components, SpatialFluxComponent):
-            components = {self._default_flux_component: components}
-        components = FluxComponents(components)
+        components = self._as_components(components)
         _hip.lib()
         with torch.cuda.device(self.device):
             return FitSession(self, datasets, datasets_validation, components, dist or DistContext.current(),
@@ -514,6 +574,22 @@ class FitSession:
         # (sharded joint fit: a dataset's calibration lives -- parameters, gradients, its small optimizer -- on the rank
         # that owns the dataset; `gather_calibrations` hands the values to every rank for results and checkpoints)
         self.calibrations = calibrations
+        sparse = [name for name, c in components.items() if getattr(c, "is_sparse", False)]
+        self.has_sparse = bool(sparse)
+        if sparse and dist.sharded:
+            raise NotImplementedError(
+                f"a sharded fit (several ranks) with the sparse flux component {sparse[0]!r} is not implemented in "
+                "jolideco_amd: run it in one process"
+            )
+        if sparse and deconvolver.compute_error:
+            raise NotImplementedError(
+                f"compute_error=True with the sparse flux component {sparse[0]!r} is not implemented in jolideco_amd"
+            )
+        if sparse and deconvolver.checkpoint_path is not None:
+            raise NotImplementedError(
+                f"checkpoints are ASDF files, which cannot carry the sparse flux component {sparse[0]!r}: fit without "
+                "checkpoint_path and write the result in the FITS format"
+            )
         device = deconvolver.device
         self.components = components = components.to(device)
         self.joint = deconvolver.fit_mode == "joint"
@@ -577,12 +653,13 @@ class FitSession:
         self.n_val = val.n_datasets if val else 0
         # ONE flat buffer = [flux gradients of all components | scalars of one epoch] so that the
         # joint step needs a single all-reduce.
-        numels = [c._flux_upsampled.numel() for c in components.values()]
+        numels = [int(np.prod(c.shape[-2:])) for c in components.values()]
         n_scalars = self.n_d + self.n_c + self.n_val
         self.comm = torch.zeros(sum(numels) + n_scalars, dtype=torch.float32, device=device)
         offsets = np.concatenate([[0], np.cumsum(numels)])
         self.states = [
-            _ComponentState(name, comp, self.comm[offsets[i] : offsets[i + 1]])
+            _SparseComponentState(name, comp, self.comm[offsets[i] : offsets[i + 1]], deconvolver)
+            if getattr(comp, "is_sparse", False) else _ComponentState(name, comp, self.comm[offsets[i] : offsets[i + 1]])
             for i, (name, comp) in enumerate(components.items())
         ]
         self.scalars = self.comm[offsets[-1] :]
@@ -778,6 +855,7 @@ class FitSession:
         session's own `_optimizer_step` (tests that replace it to record or suppress the step see every gradient)."""
         return (
             self.fuse_optimizer_step and not self.dist.sharded and not st.frozen
+            and not getattr(st, "is_sparse", False)  # (a sparse component steps its source vectors, not an image)
             and getattr(prior, "supports_fused_step", False) and getattr(prior, "stride", 0) >= 4
             and "_optimizer_step" not in vars(self.cfg)  # (a hook installed on the instance AFTER the session was built)
         )
@@ -786,7 +864,7 @@ class FitSession:
         """Sharded fits: the bands of the prior's gradient are added and the optimizer step applied in one launch
         (jd_add_rolled_bands_step) -- not frozen, width a multiple of 4 and 16-byte aligned images, the session's own
         `_optimizer_step`, no JOLIDECO_NO_FUSED_STEP."""
-        if st.frozen or not self.fuse_optimizer_step or "_optimizer_step" in vars(self.cfg):
+        if st.frozen or getattr(st, "is_sparse", False) or not self.fuse_optimizer_step or "_optimizer_step" in vars(self.cfg):
             return False
         images = [st.theta, st.flux[0], st.flux[1], st.grad, getattr(st, "exp_avg", None), getattr(st, "exp_avg_sq", None), st.mask]
         return st.grad.shape[-1] % 4 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in images)
@@ -828,7 +906,10 @@ class FitSession:
 
     def _planned_capable(self):
         """Planned epochs apply: one process, the session's own optimizer step (a hook sees every gradient through the
-        by-value path), no event brackets around collectives, no kernel timers."""
+        by-value path), no event brackets around collectives, no kernel timers, no sparse component (its stepper takes
+        its bias terms by value: by-value epochs only, nothing is captured)."""
+        if self.has_sparse:
+            return False
         cfg = self.cfg
         own = getattr(type(cfg), "_optimizer_step", None) is MAPDeconvolver._optimizer_step and "_optimizer_step" not in vars(cfg)
         return (self._planned_ok and own and not self.dist.sharded and self.comm_events is None and not self.n_val
@@ -1461,6 +1542,9 @@ def _write_map_result_to_npz(result, filename, overwrite):
     filename = Path(filename)
     if filename.exists() and not overwrite:
         raise OSError(f"{filename} exists")
+    from .utils.io.asdf import refuse_sparse
+
+    refuse_sparse(result.components, "an npz result")
     arrays = {f"flux/{name}": flux for name, flux in result.components.to_numpy().items()}
     for name, component in result.components.items():
         arrays[f"meta/{name}"] = np.array(

@@ -161,6 +161,8 @@ extern "C" const char* jd_kernel_name(int kernel) {
     case JD_KERNEL_ELEMENTWISE_SUBPIX: return "elementwise_prior_subpix_kernel";
     case JD_KERNEL_SMOOTHNESS: return "smoothness_prior_kernel";
     case JD_KERNEL_ELEMENTWISE_PRIOR: return "elementwise_prior_kernel";
+    case JD_KERNEL_SPARSE_RENDER: return "sparse_render_kernel";
+    case JD_KERNEL_SPARSE_BACKWARD: return "sparse_backward_kernel";
     default: return "?";
   }
 }

@@ -1,4 +1,4 @@
-from .core import FluxComponents, SpatialFluxComponent
+from .core import FluxComponents, SparseSpatialFluxComponent, SpatialFluxComponent
 from .npred import NPredCalibration, NPredCalibrations, NPredModel, NPredModels
 
-__all__ = ["FluxComponents", "SpatialFluxComponent", "NPredModel", "NPredModels", "NPredCalibration", "NPredCalibrations"]
+__all__ = ["FluxComponents", "SpatialFluxComponent", "SparseSpatialFluxComponent", "NPredModel", "NPredModels", "NPredCalibration", "NPredCalibrations"]

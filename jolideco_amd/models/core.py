@@ -1,9 +1,12 @@
-"""Flux components (reference: jolideco/models/core.py:354-607,720-842).
+"""Flux components (reference: jolideco/models/core.py:54-342,354-607,720-842).
 
 A `SpatialFluxComponent` owns the log-flux parameter theta as an `nn.Parameter` so that user code
 that inspects `.parameters()` keeps working.  During a fit the parameter, its flux image, the
 gradient accumulator and the optimizer moments live on the HIP device and are updated by the fused
 kernels (csrc/elementwise.hip); `flux_upsampled` is the autograd-visible `exp(theta) [* mask]`.
+
+A `SparseSpatialFluxComponent` is a list of point sources (flux, x, y) with trainable positions; its flux image is
+rendered by csrc/sparse.hip (`ops.SparseRenderFunction`: differentiable with respect to the three parameter vectors).
 """
 import logging
 from pathlib import Path
@@ -19,11 +22,13 @@ from ..utils.io import (
     IO_FORMATS_FLUX_COMPONENT_WRITE,
     IO_FORMATS_FLUX_COMPONENTS_READ,
     IO_FORMATS_FLUX_COMPONENTS_WRITE,
+    IO_FORMATS_SPARSE_FLUX_COMPONENT_READ,
+    IO_FORMATS_SPARSE_FLUX_COMPONENT_WRITE,
     get_reader,
     get_writer,
 )
 
-__all__ = ["SpatialFluxComponent", "FluxComponents"]
+__all__ = ["SpatialFluxComponent", "FluxComponents", "SparseSpatialFluxComponent"]
 
 log = logging.getLogger(__name__)
 
@@ -36,6 +41,133 @@ def parse_flux_tensor(value, cls):
     if not isinstance(value, torch.Tensor):
         return torch.from_numpy(np.asarray(value)[np.newaxis, np.newaxis].astype(np.float32))
     return value
+
+
+class SparseSpatialFluxComponent(nn.Module):
+    """Sparse flux component: a list of point sources (reference: models/core.py:54-342).
+
+    Parameters
+    ----------
+    flux : `~torch.Tensor`
+        Initial fluxes, shape (N,).
+    x_pos, y_pos : `~torch.Tensor`
+        Positions in pixel coordinates, shape (N,), pixel centres at integers.  As in the reference, whose `flux` unpacks
+        its index grids as ``y, x = self.indices`` (models/core.py:198-223), ``x_pos`` runs along the FIRST image axis
+        (rows, ``shape[0]``) and ``y_pos`` along the second (columns): a source at ``x_pos = 2, y_pos = 7.25`` lights
+        ``image[2, 7]`` and ``image[2, 8]``.  Files and fits written by either package mean the same pixels.
+    shape : tuple of int
+        Image shape (H, W).
+    use_log_flux : bool
+        Optimise log(flux) (default); False optimises the flux itself.
+    prior : `Prior`
+        Prior on the rendered image (default uniform).
+    frozen : bool
+        Exclude the component from the optimisation.
+    """
+
+    is_sparse = True
+    upsampling_factor = 1
+
+    def __init__(self, flux, x_pos, y_pos, shape, use_log_flux=True, prior=None, frozen=False, wcs=None):
+        super().__init__()
+        flux, x_pos, y_pos = (torch.as_tensor(v).type(torch.float32).reshape(-1) for v in (flux, x_pos, y_pos))
+        if not flux.numel() == x_pos.numel() == y_pos.numel() or flux.numel() < 1:
+            raise ValueError(
+                f"flux, x_pos and y_pos need the same length (at least one source), got {flux.numel()}, "
+                f"{x_pos.numel()} and {y_pos.numel()}"
+            )
+        shape = tuple(int(v) for v in shape)
+        if len(shape) != 2 or min(shape) < 1:
+            raise ValueError(f"shape must be the (H, W) of the image, got {shape}")
+        if use_log_flux:
+            flux = torch.log(flux)
+        self.prior = prior if prior is not None else UniformPrior()
+        self.frozen = frozen
+        self._wcs = wcs
+        self._shape = shape
+        self._flux = nn.Parameter(flux)
+        self.x_pos = nn.Parameter(x_pos.clone())
+        self.y_pos = nn.Parameter(y_pos.clone())
+        self._use_log_flux = bool(use_log_flux)
+
+    @classmethod
+    def from_numpy(cls, flux, x_pos, y_pos, **kwargs):
+        """Create from numpy arrays or scalars (reference: models/core.py:139-167)."""
+        flux, x_pos, y_pos = (
+            torch.from_numpy(np.atleast_1d(v).astype(np.float32)) for v in (flux, x_pos, y_pos)
+        )
+        return cls(flux=flux, x_pos=x_pos, y_pos=y_pos, **kwargs)
+
+    def parameters(self, recurse=True):
+        return [] if self.frozen else super().parameters(recurse)
+
+    @property
+    def wcs(self):
+        return self._wcs
+
+    @property
+    def shape(self):
+        return (1, 1) + self._shape
+
+    @property
+    def shape_image(self):
+        return self._shape
+
+    @property
+    def use_log_flux(self):
+        return self._use_log_flux
+
+    @property
+    def x_pos_numpy(self):
+        return self.x_pos.detach().cpu().numpy()
+
+    @property
+    def y_pos_numpy(self):
+        return self.y_pos.detach().cpu().numpy()
+
+    @property
+    def flux(self):
+        """(1, 1, H, W) image sum_n wx_n wy_n f_n, rendered on the device on every access and differentiable with
+        respect to the flux parameter and the positions (models/core.py:216-232)."""
+        from ..ops import SparseRenderFunction
+
+        # (the kernel's first coordinate runs along the columns: that is `y_pos` here, see the class docstring)
+        return SparseRenderFunction.apply(self._flux, self.y_pos, self.x_pos, self._shape, self._use_log_flux)
+
+    @property
+    def flux_upsampled(self):
+        return self.flux
+
+    @property
+    def flux_numpy(self):
+        return self.flux.detach().cpu().numpy()[0, 0]
+
+    @property
+    def flux_upsampled_numpy(self):
+        return self.flux_numpy
+
+    def to_dict(self, **kwargs):
+        """Settings and the source list, the fluxes linear (reference: models/core.py:272-295)."""
+        flux = torch.exp(self._flux) if self._use_log_flux else self._flux
+        return {
+            "use_log_flux": self._use_log_flux,
+            "frozen": self.frozen,
+            "shape": self.shape,
+            "flux": flux.detach().cpu().numpy(),
+            "x_pos": self.x_pos_numpy,
+            "y_pos": self.y_pos_numpy,
+            "prior": self.prior.to_dict(),
+        }
+
+    @classmethod
+    def read(cls, filename, format=None):
+        """Read a sparse flux component; format : {"fits"} (default: from the suffix)."""
+        return get_reader(filename, format, IO_FORMATS_SPARSE_FLUX_COMPONENT_READ)(filename)
+
+    def write(self, filename, format=None, overwrite=False, **kwargs):
+        """Write the sparse flux component; format : {"fits"} (default: from the suffix)."""
+        writer = get_writer(filename, format, IO_FORMATS_SPARSE_FLUX_COMPONENT_WRITE)
+        return writer(flux_component=self, filename=filename, overwrite=overwrite, **kwargs)
 
 
 class SpatialFluxComponent(nn.Module):

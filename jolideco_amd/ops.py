@@ -631,6 +631,70 @@ class SmoothnessPriorFunction(torch.autograd.Function):
         return (ctx.grad * grad_value).reshape(ctx.shape), None, None
 
 
+def _sparse_vectors(param, x_pos, y_pos):
+    param = require_hip_tensor(param, "flux parameter")
+    n = param.numel()
+    for name, t in (("x_pos", x_pos), ("y_pos", y_pos)):
+        require_hip_tensor(t, name)
+        if t.numel() != n:
+            raise ValueError(f"{name} holds {t.numel()} values for {n} sources")
+    limit = _hip.lib().jd_sparse_max_sources()
+    if not 1 <= n <= limit:
+        raise ValueError(f"a sparse flux component holds 1 to {limit} sources, got {n}")
+    return n
+
+
+def sparse_render(param, x_pos, y_pos, use_log_flux, out):
+    """out (H, W) <- the image of the point sources (jd_sparse_render): sum_n wx_n wy_n f_n with the bilinear weights of
+    the reference's `grid_weights`, f = exp(param) for ``use_log_flux``; every pixel is written."""
+    n = _sparse_vectors(param, x_pos, y_pos)
+    out = require_hip_tensor(out, "out")
+    H, W = out.shape[-2:]
+    if out.numel() != H * W:
+        raise ValueError("out must be a single (H, W) image")
+    check(_hip.lib().jd_sparse_render(ptr(param), ptr(x_pos), ptr(y_pos), n, int(bool(use_log_flux)), int(H), int(W), ptr(out),
+                                      stream_ptr(out.device)))
+    return out
+
+
+def sparse_backward(param, x_pos, y_pos, use_log_flux, grad_image, grad_param, grad_x, grad_y):
+    """(grad_param, grad_x, grad_y) <- the gradients of the three vectors given ``grad_image`` = d loss / d image
+    (jd_sparse_backward); assigned, not accumulated."""
+    n = _sparse_vectors(param, x_pos, y_pos)
+    grad_image = require_hip_tensor(grad_image, "grad_image")
+    H, W = grad_image.shape[-2:]
+    if grad_image.numel() != H * W:
+        raise ValueError("grad_image must be a single (H, W) image")
+    for t in (grad_param, grad_x, grad_y):
+        if require_hip_tensor(t, "gradient vector").numel() != n:
+            raise ValueError("gradient vectors must hold one value per source")
+    check(_hip.lib().jd_sparse_backward(ptr(param), ptr(x_pos), ptr(y_pos), n, int(bool(use_log_flux)), int(H), int(W),
+                                        ptr(grad_image), ptr(grad_param), ptr(grad_x), ptr(grad_y),
+                                        stream_ptr(grad_image.device)))
+
+
+class SparseRenderFunction(torch.autograd.Function):
+    """(1, 1, H, W) image of a sparse flux component, differentiable with respect to its flux parameter and positions
+    (models/core.py:216-232)."""
+
+    @staticmethod
+    def forward(ctx, param, x_pos, y_pos, shape, use_log_flux):
+        H, W = (int(v) for v in shape)
+        image = torch.empty((1, 1, H, W), dtype=torch.float32, device=param.device)
+        vectors = [v.detach().contiguous() for v in (param, x_pos, y_pos)]
+        sparse_render(*vectors, use_log_flux, image)
+        ctx.save_for_backward(*vectors)
+        ctx.use_log_flux = use_log_flux
+        return image
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        param, x_pos, y_pos = ctx.saved_tensors
+        grads = [torch.empty_like(param) for _ in range(3)]
+        sparse_backward(param, x_pos, y_pos, ctx.use_log_flux, grad_image.contiguous(), *grads)
+        return grads[0], grads[1], grads[2], None, None
+
+
 def band_rows(patch_rows, stride, H, patch=8):
     """Pixel rows [y_begin, y_end) of the rolled frame that the patch rows ``patch_rows = (begin, end)`` cover
     (``end < 0``: up to the last patch row); an empty shard covers no row."""

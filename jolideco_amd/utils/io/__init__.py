@@ -18,10 +18,12 @@ from .fits import (
     read_flux_components_from_fits,
     read_map_result_from_fits,
     read_npred_calibrations_from_fits,
+    read_sparse_flux_component_from_fits,
     write_flux_component_to_fits,
     write_flux_components_to_fits,
     write_map_result_to_fits,
     write_npred_calibrations_to_fits,
+    write_sparse_flux_component_to_fits,
 )
 from .yaml import (
     read_flux_component_from_yaml,
@@ -42,6 +44,8 @@ __all__ = [
     "IO_FORMATS_FLUX_COMPONENT_WRITE",
     "IO_FORMATS_FLUX_COMPONENTS_READ",
     "IO_FORMATS_FLUX_COMPONENTS_WRITE",
+    "IO_FORMATS_SPARSE_FLUX_COMPONENT_READ",
+    "IO_FORMATS_SPARSE_FLUX_COMPONENT_WRITE",
     "IO_FORMATS_NPRED_CALIBRATIONS_READ",
     "IO_FORMATS_NPRED_CALIBRATIONS_WRITE",
 ]
@@ -96,6 +100,10 @@ IO_FORMATS_FLUX_COMPONENTS_WRITE = {
     "asdf": write_flux_components_to_asdf,
     "yaml": write_flux_components_to_yaml,
 }
+
+# a source list is a table: FITS only (reference: utils/io/__init__.py)
+IO_FORMATS_SPARSE_FLUX_COMPONENT_READ = {"fits": read_sparse_flux_component_from_fits}
+IO_FORMATS_SPARSE_FLUX_COMPONENT_WRITE = {"fits": write_sparse_flux_component_to_fits}
 
 IO_FORMATS_NPRED_CALIBRATIONS_READ = {
     "yaml": read_npred_calibrations_from_yaml,

@@ -24,6 +24,17 @@ __all__ = [
 ]
 
 
+def refuse_sparse(components, what):
+    """ASDF / YAML / npz trees hold images, not source tables: a sparse flux component goes to FITS."""
+    members = components.items() if hasattr(components, "items") else [("component", components)]
+    for name, component in members:
+        if getattr(component, "is_sparse", False):
+            raise NotImplementedError(
+                f"{what} cannot carry the sparse flux component {name!r} (a SparseSpatialFluxComponent is a table of "
+                "sources): write it in the FITS format"
+            )
+
+
 def _write(tree, filename, overwrite):
     path = Path(filename)
     if path.exists() and not overwrite:
@@ -34,6 +45,7 @@ def _write(tree, filename, overwrite):
 
 def write_flux_component_to_asdf(flux_component, filename, overwrite, **kwargs):
     """Flux component(s) -> ASDF: the tree is ``to_dict(include_data="numpy")`` (reference: asdf.py:9-39)."""
+    refuse_sparse(flux_component, "the ASDF format")
     _write(flux_component.to_dict(include_data="numpy"), filename, overwrite)
 
 
@@ -59,6 +71,7 @@ def read_flux_components_from_asdf(filename):
 def write_map_result_to_asdf(result, filename, overwrite, **kwargs):
     """`MAPDeconvolverResult` -> ASDF (reference: asdf.py:112-142): components, initial components, the loss trace as a
     table, the configuration."""
+    refuse_sparse(result.components, "an ASDF result or checkpoint")
     tree = {"components": result.components.to_dict(include_data="numpy")}
     if result.components_init is not None:
         tree["components-init"] = result.components_init.to_dict(include_data="numpy")

@@ -9,9 +9,9 @@ written by either package open in the other:
   and a one-row ``CONFIG`` table;
 * flux components (fits.py:299-333): PRIMARY + one IMAGE HDU per component;
 * one flux component (fits.py:335-383): the image in the primary HDU (``EXTNAME = 'PRIMARY'``);
-* calibrations (fits.py:386-418): a table with ``name`` and one column per calibration parameter.
-
-Sparse (point source list) components are not on the accelerated path; their table HDUs raise.
+* calibrations (fits.py:386-418): a table with ``name`` and one column per calibration parameter;
+* a sparse (point source list) component (fits.py:43-113): a binary table HDU with the columns ``x_pos``, ``y_pos``,
+  ``flux`` (linear) and the image shape in ``IMSHAPE1`` / ``IMSHAPE2``.
 """
 import logging
 
@@ -101,10 +101,44 @@ def flux_component_from_image_hdu(hdu):
     return SpatialFluxComponent.from_dict(unflatten_dict(data, sep=META_SEP))
 
 
+def sparse_flux_component_to_table_hdu(flux_component, name):
+    """Sparse flux component -> table HDU (reference: fits.py:43-84)."""
+    header = Header()
+    for key, value in (flux_component.wcs or {}).items():
+        header[key] = value
+    data = flux_component.to_dict()
+    table = FitsTable()
+    for column in ("x_pos", "y_pos", "flux"):
+        table[column] = np.atleast_1d(data.pop(column))
+    shape = data.pop("shape")
+    header["IMSHAPE1"] = int(shape[-2])
+    header["IMSHAPE2"] = int(shape[-1])
+    for key, value in flatten_dict(data, sep=META_SEP).items():
+        if key not in FITS_META:
+            raise KeyError(f"no FITS keyword is defined for the component setting {key!r}")
+        header[FITS_META[key]] = value
+    return HDU(data=table, header=header, name=name.upper(), kind="bintable")
+
+
 def sparse_flux_component_from_table_hdu(hdu):
-    raise NotImplementedError(
-        f"HDU {hdu.name!r} holds a sparse (point source list) flux component (reference fits.py:87-112); "
-        "sparse components are not implemented in jolideco_amd"
+    """Table HDU -> sparse flux component (reference: fits.py:87-112; the prior's keys are read back as well, where the
+    reference leaves the default prior)."""
+    from ...models import SparseSpatialFluxComponent
+    from ...priors import Prior
+    from ...priors.patches.gmm import GMMNotAvailableError
+
+    table, header = hdu.data, hdu.header
+    meta = {key: header.get(fits_key) for fits_key, key in FITS_META_INVERSE.items() if header.get(fits_key) is not None}
+    prior = None
+    prior_data = unflatten_dict(meta, sep=META_SEP).get("prior")
+    if prior_data:
+        try:
+            prior = Prior.from_dict(prior_data)
+        except GMMNotAvailableError as error:
+            log.warning(f"{error}; the component gets a uniform prior instead of {prior_data.get('type')}")
+    return SparseSpatialFluxComponent.from_numpy(
+        x_pos=table["x_pos"], y_pos=table["y_pos"], flux=table["flux"], shape=(header["IMSHAPE1"], header["IMSHAPE2"]),
+        use_log_flux=bool(header["LOG_FLUX"]), frozen=bool(header["FROZEN"]), prior=prior, wcs=wcs_from_header(header),
     )
 
 
@@ -113,8 +147,9 @@ def flux_components_to_hdulist(flux_components, name_suffix=""):
     hdus = []
     for name, component in flux_components.items():
         if getattr(component, "is_sparse", False):
-            raise NotImplementedError("sparse flux components are not implemented in jolideco_amd")
-        hdus.append(flux_component_to_image_hdu(component, name=name + name_suffix))
+            hdus.append(sparse_flux_component_to_table_hdu(component, name=name + name_suffix))
+        else:
+            hdus.append(flux_component_to_image_hdu(component, name=name + name_suffix))
     return hdus
 
 
@@ -168,11 +203,27 @@ def read_flux_components_from_fits(filename):
 def write_flux_component_to_fits(flux_component, filename, overwrite):
     """The component image goes into the primary HDU (reference: fits.py:335-359)."""
     if getattr(flux_component, "is_sparse", False):
-        raise NotImplementedError("sparse flux components are not implemented in jolideco_amd")
+        return write_sparse_flux_component_to_fits(flux_component, filename, overwrite)
     hdu = flux_component_to_image_hdu(flux_component, name="primary")
     hdu.kind = "primary"
     log.info(f"writing {filename}")
     write_fits(filename, [hdu], overwrite=overwrite)
+
+
+def write_sparse_flux_component_to_fits(flux_component, filename, overwrite):
+    """The source table behind an empty primary HDU (a table cannot be the first HDU of a file; reference:
+    fits.py:347-359)."""
+    hdu = sparse_flux_component_to_table_hdu(flux_component, name="primary")
+    log.info(f"writing {filename}")
+    write_fits(filename, [HDU(kind="primary"), hdu], overwrite=overwrite)
+
+
+def read_sparse_flux_component_from_fits(filename):
+    """The first table HDU of the file as a sparse flux component."""
+    tables = [hdu for hdu in read_fits(filename) if hdu.kind == "bintable"]
+    if not tables:
+        raise ValueError(f"{filename} holds no table")
+    return sparse_flux_component_from_table_hdu(tables[0])
 
 
 def read_flux_component_from_fits(filename, hdu_name=0):
