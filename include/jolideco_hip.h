@@ -214,6 +214,28 @@ int jd_npred_poisson_batch_fwd_bwd(jd_conv_plan* plan, int n_datasets, const flo
                                    float* const* loss_out, float* grad_flux, int accumulate, float grad_scale,
                                    void* stream);
 
+/* jd_npred_poisson_batch_fwd_bwd (accumulate = 0, grad_flux required) that may leave part of the gradient in images of its
+ * own.  Where the datasets' PSFs walk in both strip-walk frames (17 and 33 taps), all datasets of one frame come in front
+ * of all of the other and the second frame has m <= JD_ADDEND_MAX datasets, the adjoints of those m datasets are not added
+ * into grad_flux: dataset (n_datasets - m + i) writes grad_scale * exposure * corr(g, psf) -- the very number the call
+ * above adds -- to addends[i], in a launch of its own that runs beside the first frame's adjoint launch on stream2.
+ * *n_addends <- m, and the gradient of the step is
+ *     ((grad_flux + addends[0]) + addends[1]) + ...        in this order: the bits of jd_npred_poisson_batch_fwd_bwd,
+ * which jd_adam_step_addends and jd_gmm_prior_fwd_bwd_step (jd_step.addend) form while they read the gradient.
+ * Everywhere else (one frame, frames interleaved, more late datasets than images, other kernels, option
+ * JD_SEP_ADJ_ADDENDS = 0) the call IS jd_npred_poisson_batch_fwd_bwd and *n_addends <- 0.
+ *   addends : host array of JD_ADDEND_MAX device images (H x W floats, 16-byte aligned), the leading non-null ones usable
+ *   stream2 : nullable (then everything runs on stream).  The call forks stream2 behind the forward launch on stream and
+ *             joins it into stream before it returns: work enqueued on stream afterwards sees the addends complete, and a
+ *             stream capture sees a closed parallel branch.  stream2 must not be the stream of other work of the step. */
+#define JD_ADDEND_MAX 4
+int jd_npred_poisson_batch_addends_fwd_bwd(jd_conv_plan* plan, int n_datasets, const float* flux,
+                                           const float* const* exposure, const float* const* khat,
+                                           const float* const* background, const float* const* counts,
+                                           const float* stirling_mean, float eps, float* const* loss_out, float* grad_flux,
+                                           int accumulate, float grad_scale, float* const* addends, void* stream2,
+                                           int* n_addends, void* stream);
+
 /* The batched joint step for SEVERAL flux components (NPredModels.evaluate sums the per-component models after their
  * clip, models/npred.py:210-261; per-component PSF / exposure as in npred.py:281-295): dataset d convolves flux[c] with
  * khat[d * n_components + c] after scaling by exposure[d * n_components + c]; one forward launch (grid.y = dataset, the
@@ -377,6 +399,9 @@ typedef struct {
   int use_log_flux, sgd;
   const float* bias_dev;  /* nullable, device [2] = {step_size, bias2_sqrt}: read by the kernel instead of the two members
                              above (the step count of a captured graph's optimizer step lives in device memory) */
+  const float* addend[JD_ADDEND_MAX]; /* the leading non-null entries: images added to grad_flux in this order before the
+                             prior's term, g = (grad_flux + addend[0]) + addend[1] ... (what
+                             jd_npred_poisson_batch_addends_fwd_bwd left out of grad_flux); all null: none */
 } jd_step;
 int jd_gmm_prior_fwd_bwd_step(jd_gmm* gmm, const float* flux, int H, int W, int stride, int shift_y, int shift_x,
                               int marginalize, float value_scale, float* value_out, int accumulate_value,
@@ -483,6 +508,12 @@ int jd_adam_step(float* theta, const float* flux_in, float* flux_out, float* gra
                  float* exp_avg_sq, const float* mask, size_t n, float step_size, float beta1,
                  float beta2, float one_minus_beta1, float one_minus_beta2, float bias2_sqrt, float eps,
                  int zero_grad, int use_log_flux, const float* bias_dev, void* stream);
+/* jd_adam_step on the gradient ((grad_flux + addends[0]) + addends[1]) + ... -- the leading non-null entries of the host
+ * array addends[JD_ADDEND_MAX], device images of n floats (jd_npred_poisson_batch_addends_fwd_bwd); they are only read. */
+int jd_adam_step_addends(float* theta, const float* flux_in, float* flux_out, float* grad_flux, float* exp_avg,
+                         float* exp_avg_sq, const float* mask, size_t n, float step_size, float beta1,
+                         float beta2, float one_minus_beta1, float one_minus_beta2, float bias2_sqrt, float eps,
+                         int zero_grad, int use_log_flux, const float* bias_dev, const float* const* addends, void* stream);
 /* jd_adam_step with use_log_flux = 0 for MANY small parameter vectors in ONE launch (the calibration parameters of the
  * datasets of a joint step, jolideco/core.py:197-204,229): tensor i (sizes[i] floats) takes its own step_size[i] /
  * bias2_sqrt[i] (its own step count, as torch.optim.Adam keeps one per parameter).  Host arrays of n_tensors <= 64

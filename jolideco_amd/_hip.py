@@ -70,6 +70,11 @@ EXPORTS = {
         c_int,
         [c_void_p, c_int, c_void_p, fpp, fpp, fpp, fpp, fp, c_float, fpp, c_void_p, c_int, c_float, c_void_p],
     ),
+    "jd_npred_poisson_batch_addends_fwd_bwd": (
+        c_int,
+        [c_void_p, c_int, c_void_p, fpp, fpp, fpp, fpp, fp, c_float, fpp, c_void_p, c_int, c_float, fpp, c_void_p,
+         POINTER(c_int), c_void_p],
+    ),
     "jd_npred_poisson_batch_multi_fwd_bwd": (
         c_int,
         [c_void_p, c_int, c_int, fpp, fpp, fpp, fpp, fpp, fp, c_float, fpp, fpp, c_int, c_float, c_void_p],
@@ -122,6 +127,11 @@ EXPORTS = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float,
          c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p],
     ),
+    "jd_adam_step_addends": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float,
+         c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, fpp, c_void_p],
+    ),
     "jd_adam_step_multi": (
         c_int,
         [c_int, fpp, fpp, fpp, fpp, POINTER(c_int), fp, fp, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p],
@@ -140,6 +150,9 @@ EXPORTS = {
     "jd_clock_probe": (c_int, [c_double, POINTER(c_double), c_void_p]),
 }
 
+ADDEND_MAX = 4  # JD_ADDEND_MAX of include/jolideco_hip.h
+
+
 class Step(ctypes.Structure):
     """`jd_step` of include/jolideco_hip.h: the optimizer step a prior evaluation applies in its epilogue."""
 
@@ -148,7 +161,7 @@ class Step(ctypes.Structure):
         ("exp_avg_sq", c_void_p), ("mask", c_void_p),
         ("step_size", c_float), ("beta1", c_float), ("beta2", c_float), ("one_minus_beta1", c_float),
         ("one_minus_beta2", c_float), ("bias2_sqrt", c_float), ("eps", c_float), ("lr", c_float),
-        ("use_log_flux", c_int), ("sgd", c_int), ("bias_dev", c_void_p),
+        ("use_log_flux", c_int), ("sgd", c_int), ("bias_dev", c_void_p), ("addend", c_void_p * ADDEND_MAX),
     ]
 
 

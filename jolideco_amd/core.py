@@ -236,6 +236,8 @@ class MAPDeconvolver:
         args = _hip.Step()
         args.theta, args.flux_in, args.flux_out = st.theta.data_ptr(), st.flux_cur.data_ptr(), st.flux[1 - st.cur].data_ptr()
         args.grad_flux = st.grad.data_ptr()
+        for k, image in enumerate(getattr(st, "addends", ())):  # (the part of this step's gradient left beside `grad`)
+            args.addend[k] = image.data_ptr()
         args.mask = None if st.mask is None else st.mask.data_ptr()
         args.use_log_flux = int(st.use_log_flux)
         if self.optimizer_type == "adam":
@@ -726,6 +728,11 @@ class FitSession:
         side_priority = int(os.environ.get("JOLIDECO_PRIOR_STREAM_PRIORITY", "0"))
         self._side_stream = (torch.cuda.Stream(device=device, priority=side_priority)
                              if torch.device(device).type == "cuda" else None)
+        # the adjoints of a joint step's second PSF frame beside those of the first (`_likelihood_addends`): a stream of its
+        # own (the side stream runs the prior's first phase at that time) and the images they are left in
+        self._addend_stream = None
+        self._addend_images = None  # (None: not looked at yet; []: this fit has no use for them)
+        self.addends_used = 0  # images the last joint step's gradient was spread over besides `grad` (0: `grad` holds it all)
         self.step_scalars = None
         self._graphs = {}
         self._epochs_done = 0
@@ -1002,6 +1009,52 @@ class FitSession:
         return {"shifts": shifts, "flux_bias": [None] * n_flux, "cal_bias": [None] * len(cal_groups), "cal_items": cal_items,
                 "n_steps": n_flux, "signature": ()}
 
+    # ---- the second frame's adjoints beside the first's -----------------------------------------------------------------
+    def _likelihood_addends(self, early):
+        """Images the batched likelihood call of a joint step may leave the adjoints of its second PSF frame in
+        (`ConvPlan.npred_poisson_batch_fwd_bwd`), or None.  ``early``: the components whose prior's first phase
+        `_start_priors` has put on the side stream for this step.  Whoever reads the gradient then adds the images, in
+        order, BEFORE any other term -- the additions the adjoint launch would have made -- so this holds only where the next
+        reader of the gradient image is an optimizer step that does: one dense component, one process (an all-reduce needs
+        the total), and a prior that applies the session's own step in its gather kernel."""
+        if not (self.batch_joint and self.n_c == 1 and not self.dist.sharded and self.dist.world_size == 1):
+            return None
+        st, prior = self.states[0], self.priors[0]
+        if st.frozen or getattr(st, "is_sparse", False) or "_optimizer_step" in vars(self.cfg):
+            return None
+        # Only where a prior's first phase really runs beside the likelihood launches of this step.  With nothing beside them
+        # (the prior behind the likelihood, a prior without kernels, a by-value epoch) the two adjoints side by side end
+        # LATER than one after the other -- the strip walks are bound by their SIMDs' issue slots, not by free wave slots
+        # (profiles/adjoint_addends/README.md: last adjoint done 259 us after the forward launch's start against 245) --
+        # and the accumulating launches stay.
+        if 0 not in early or not self._fuse_step(st, prior):
+            return None
+        if st.grad.shape[-1] % 4 or len(self.local_idx) > 16:
+            return None
+        if self._addend_images is None:  # once: the operators of a session stay
+            models = self.total_loss.poisson_loss.npred_models_all
+            frames = [models[li][st.name].plan.walk_frame(models[li][st.name].khat) for _, li in self.local_idx]
+            late = sum(1 for f in frames if f != frames[0])
+            self._addend_images = []
+            if 0 < late <= _hip.ADDEND_MAX and all(f != frames[0] for f in frames[-late:]):
+                self._addend_images = [torch.empty_like(st.grad) for _ in range(late)]
+                self._addend_stream = torch.cuda.Stream(device=st.grad.device)
+        return self._addend_images or None
+
+    def _joint_likelihood(self, fluxes, grads, early=()):
+        """The batched likelihood call of a joint step (gradient OVERWRITTEN); the images part of the gradient was left in
+        are handed to the fused step that follows (`_step_args`).  ``early``: what `_start_priors` returned for the step."""
+        n_c = self.n_c
+        addends = self._likelihood_addends(early)
+        beside = None if addends is None else self._addend_stream
+        used = self.total_loss.poisson_loss.fwd_bwd_batch(
+            [li for _, li in self.local_idx], fluxes if n_c > 1 else fluxes[0],
+            [self._slot(gslot) for gslot, _ in self.local_idx], grad=grads if n_c > 1 else grads[0], accumulate=False,
+            flux_nonneg=self.flux_nonneg, addends=addends, side_stream=beside,
+        )
+        self.addends_used = used or 0
+        self.states[0].addends = tuple(addends[: self.addends_used]) if self.addends_used else ()
+
     # ---- the prior beside the likelihood ------------------------------------------------------------------------------
     def _overlap_active(self):
         """Phase 1 of a GMM prior (value + gradient rows: it reads the flux only) runs on a second stream while the main
@@ -1021,9 +1074,11 @@ class FitSession:
             kwargs = {"shifts": shifts[ci]} if ci in shifts else {}
             flux, value = st.flux_cur, slot(n_d + ci)
             if self._fuse_step(st, prior):
-                args = cfg._step_args(st, step_no, bias)
 
-                def call(phases=3, prior=prior, flux=flux, value=value, args=args, kwargs=kwargs):
+                def call(phases=3, prior=prior, flux=flux, value=value, st=st, kwargs=kwargs):
+                    # (the step's arguments as they are when the call is MADE: the gather of phase 2 comes behind the
+                    # likelihood call of the step, which says where the rest of the gradient lies -- `_joint_likelihood`)
+                    args = cfg._step_args(st, step_no, bias)
                     prior.device_fwd_bwd_step(flux, value, coef, args, **(dict(kwargs, phases=phases) if phases != 3 else kwargs))
 
                 calls.append((ci, call, True))
@@ -1154,11 +1209,7 @@ class FitSession:
             early = self._start_priors(calls)  # (the priors' first phase beside the likelihood launches below)
             first = True
             if self.batch_joint:
-                total_loss.poisson_loss.fwd_bwd_batch(
-                    [li for _, li in self.local_idx], fluxes if n_c > 1 else fluxes[0],
-                    [slot(gslot) for gslot, _ in self.local_idx], grad=grads if n_c > 1 else grads[0], accumulate=False,
-                    flux_nonneg=self.flux_nonneg,
-                )
+                self._joint_likelihood(fluxes, grads, early)
                 first = False
             elif self.batch_joint_calibrated:
                 for _, li in self.local_idx:
@@ -1333,11 +1384,7 @@ class FitSession:
             first = True
             if self.batch_joint:
                 # all local datasets in three launches (forward + Poisson, losses, adjoint): same numbers as the loop
-                total_loss.poisson_loss.fwd_bwd_batch(
-                    [li for _, li in self.local_idx], fluxes if n_c > 1 else fluxes[0],
-                    [slot(gslot) for gslot, _ in self.local_idx], grad=grads if n_c > 1 else grads[0], accumulate=False,
-                    flux_nonneg=self.flux_nonneg,
-                )
+                self._joint_likelihood(fluxes, grads)
                 first = False
             elif self.batch_joint_calibrated:
                 for _, li in self.local_idx:

@@ -644,7 +644,8 @@ __global__ __launch_bounds__(BLOCK) void poisson_nll_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------
 // K6: chain rule + Adam (torch.optim.Adam single-tensor formula) + exp of the new theta
 // ------------------------------------------------------------------------------------------
-template <int VEC>
+// NA: addend images (a.addend[0 .. NA) are set), added to the gradient in order before the update (jd_adam.h)
+template <int VEC, int NA>
 __global__ __launch_bounds__(BLOCK) void adam_kernel(AdamArgs a) {
   use_device_bias(a);
   const size_t stride = (size_t)gridDim.x * BLOCK * VEC;
@@ -654,6 +655,9 @@ __global__ __launch_bounds__(BLOCK) void adam_kernel(AdamArgs a) {
       const float4 t4 = *reinterpret_cast<const float4*>(a.theta + i);
       const float4 f4 = *reinterpret_cast<const float4*>(a.flux_in + i);
       const float4 g4 = *reinterpret_cast<const float4*>(a.grad_flux + i);
+      float4 a4[NA ? NA : 1];
+#pragma unroll
+      for (int k = 0; k < NA; ++k) a4[k] = *reinterpret_cast<const float4*>(a.addend[k] + i);
       th[0] = t4.x, th[1] = t4.y, th[2] = t4.z, th[3] = t4.w;
       f[0] = f4.x, f[1] = f4.y, f[2] = f4.z, f[3] = f4.w;
       gf[0] = g4.x, gf[1] = g4.y, gf[2] = g4.z, gf[3] = g4.w;
@@ -668,8 +672,12 @@ __global__ __launch_bounds__(BLOCK) void adam_kernel(AdamArgs a) {
         const float4 k4 = *reinterpret_cast<const float4*>(a.mask + i);
         mk[0] = k4.x, mk[1] = k4.y, mk[2] = k4.z, mk[3] = k4.w;
       }
+#pragma unroll
+      for (int k = 0; k < NA; ++k) gf[0] += a4[k].x, gf[1] += a4[k].y, gf[2] += a4[k].z, gf[3] += a4[k].w;
     } else {
       th[0] = a.theta[i], f[0] = a.flux_in[i], gf[0] = a.grad_flux[i];
+#pragma unroll
+      for (int k = 0; k < NA; ++k) gf[0] += a.addend[k][i];
       if (!a.sgd) m[0] = a.m[i], v[0] = a.v[i];
       mk[0] = a.mask ? a.mask[i] : 1.f;
     }
@@ -691,17 +699,31 @@ __global__ __launch_bounds__(BLOCK) void adam_kernel(AdamArgs a) {
   }
 }
 
+template <int NA>
+static void launch_adam_kernel(bool vec, unsigned blocks, const AdamArgs& a, hipStream_t stream) {
+  if (vec)
+    adam_kernel<4, NA><<<blocks, BLOCK, 0, stream>>>(a);
+  else
+    adam_kernel<1, NA><<<blocks, BLOCK, 0, stream>>>(a);
+}
+
 static int launch_adam(const AdamArgs& a, hipStream_t stream) {
-  const bool vec = (a.n % 4 == 0);
+  int na = 0;
+  while (na < ADDEND_MAX && a.addend[na]) ++na;
+  bool vec = (a.n % 4 == 0);
+  for (int k = 0; k < na; ++k) vec = vec && (reinterpret_cast<uintptr_t>(a.addend[k]) & 15) == 0;
   const size_t per_block = (size_t)BLOCK * (vec ? 4 : 1);
   size_t blocks = (a.n + per_block - 1) / per_block;
   if (blocks > 4096) blocks = 4096;
   if (blocks == 0) blocks = 1;
   ProfScope prof(JD_KERNEL_ADAM, stream);
-  if (vec)
-    adam_kernel<4><<<(unsigned)blocks, BLOCK, 0, stream>>>(a);
-  else
-    adam_kernel<1><<<(unsigned)blocks, BLOCK, 0, stream>>>(a);
+  switch (na) {
+    case 0: launch_adam_kernel<0>(vec, (unsigned)blocks, a, stream); break;
+    case 1: launch_adam_kernel<1>(vec, (unsigned)blocks, a, stream); break;
+    case 2: launch_adam_kernel<2>(vec, (unsigned)blocks, a, stream); break;
+    case 3: launch_adam_kernel<3>(vec, (unsigned)blocks, a, stream); break;
+    default: launch_adam_kernel<4>(vec, (unsigned)blocks, a, stream); break;
+  }
   JD_LAUNCH_CHECK();
   return JD_OK;
 }
@@ -1135,17 +1157,29 @@ extern "C" int jd_step_scalars_fetch(const int32_t* host_row, int32_t* dst, int 
   return JD_OK;
 }
 
-extern "C" int jd_adam_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
-                            float* exp_avg, float* exp_avg_sq, const float* mask, size_t n, float step_size,
-                            float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
-                            float bias2_sqrt, float eps, int zero_grad, int use_log_flux, const float* bias_dev,
-                            void* stream) {
+extern "C" int jd_adam_step_addends(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
+                                    float* exp_avg, float* exp_avg_sq, const float* mask, size_t n, float step_size,
+                                    float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
+                                    float bias2_sqrt, float eps, int zero_grad, int use_log_flux, const float* bias_dev,
+                                    const float* const* addends, void* stream) {
   JD_REQUIRE(theta && flux_in && flux_out && grad_flux && exp_avg && exp_avg_sq && n > 0,
              "jd_adam_step: null argument or n == 0");
   AdamArgs a{theta, flux_in, flux_out, grad_flux, exp_avg, exp_avg_sq, mask, n,
              step_size, beta1, beta2, one_minus_beta1, one_minus_beta2, bias2_sqrt, eps, 0.f, zero_grad, 0,
              use_log_flux ? 0 : 1, bias_dev};
+  static_assert(ADDEND_MAX == JD_ADDEND_MAX, "the host array of jd_adam_step_addends and AdamArgs::addend");
+  for (int k = 0; addends && k < ADDEND_MAX && addends[k]; ++k) a.addend[k] = addends[k];  // (the leading non-null entries)
   return launch_adam(a, as_stream(stream));
+}
+
+extern "C" int jd_adam_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
+                            float* exp_avg, float* exp_avg_sq, const float* mask, size_t n, float step_size,
+                            float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
+                            float bias2_sqrt, float eps, int zero_grad, int use_log_flux, const float* bias_dev,
+                            void* stream) {
+  return jd_adam_step_addends(theta, flux_in, flux_out, grad_flux, exp_avg, exp_avg_sq, mask, n, step_size, beta1, beta2,
+                              one_minus_beta1, one_minus_beta2, bias2_sqrt, eps, zero_grad, use_log_flux, bias_dev, nullptr,
+                              stream);
 }
 
 // Adam steps of MANY small parameter vectors in one launch (the calibration parameters of the datasets of a joint step:

@@ -69,6 +69,8 @@ struct jd_conv_plan {
   jd::SepBatchTable* table_dev[N_TABLES] = {};
   unsigned long long table_used[N_TABLES] = {};  // last use (call counter), 0 = empty
   unsigned long long table_clock = 0;
+  // fork / join of the addend launch of a joint step (walk_conv_adjoint_batch): created at the first such step
+  hipEvent_t addend_events[2] = {nullptr, nullptr};
 };
 
 namespace jd {
@@ -340,6 +342,8 @@ extern "C" int jd_conv_plan_destroy(jd_conv_plan* p) {
   if (p->partials_batch) (void)hipFree(p->partials_batch);
   for (auto* t : p->table_dev)
     if (t) (void)hipFree(t);
+  for (hipEvent_t e : p->addend_events)
+    if (e) (void)hipEventDestroy(e);
   for (float* g : p->gbatch)
     if (g) (void)hipFree(g);
   for (int c = 0; c < JD_MAX_COMPONENTS; ++c) {
@@ -688,13 +692,15 @@ extern "C" int jd_npred_poisson_mixed_fwd_bwd(jd_conv_plan* const* plans, int n_
   return JD_OK;
 }
 
-extern "C" int jd_npred_poisson_batch_multi_fwd_bwd(jd_conv_plan* p, int n_datasets, int n_comp, const float* const* flux,
-                                                    const float* const* exposure, const float* const* khat,
-                                                    const float* const* background, const float* const* counts,
-                                                    const float* stirling_mean, float eps, float* const* loss_out,
-                                                    float* const* grad_flux, int accumulate, float grad_scale,
-                                                    void* stream) {
-  const char* who = "jd_npred_poisson_batch_multi_fwd_bwd";
+// addends (nullable; one component, accumulate = 0): JD_ADDEND_MAX images the adjoints of the step's second PSF frame may go
+// to, *n_addends <- how many did (jd_npred_poisson_batch_addends_fwd_bwd)
+static int npred_poisson_batch_impl(const char* who, jd_conv_plan* p, int n_datasets, int n_comp, const float* const* flux,
+                                    const float* const* exposure, const float* const* khat,
+                                    const float* const* background, const float* const* counts,
+                                    const float* stirling_mean, float eps, float* const* loss_out,
+                                    float* const* grad_flux, int accumulate, float grad_scale, void* stream,
+                                    float* const* addends, void* stream2, int* n_addends) {
+  if (n_addends) *n_addends = 0;
   JD_REQUIRE(p && flux && exposure && khat && background && counts && stirling_mean && loss_out, "%s: null argument", who);
   JD_REQUIRE(p->method == JD_CONV_SEPARABLE || (p->native && n_comp == 1),
              "%s: the plan must use the separable method, or the native FFT path with one flux component (one "
@@ -788,6 +794,24 @@ extern "C" int jd_npred_poisson_batch_multi_fwd_bwd(jd_conv_plan* p, int n_datas
   for (int i = 0; i < n_datasets * n_comp; ++i) table.scale[i] = exposure[i], table.op[i] = khat[i], table.g[i] = p->gbatch[i];
   for (int d = 0; d < n_datasets; ++d) table.loss_out[d] = loss_out[d], table.loss_offset[d] = stirling_mean[d];
   walk_batch_order(table, n_datasets, n_comp, p->kh, p->kw, p->oy, p->ox);
+  // datasets of both PSF frames, the second frame's behind the first's: their adjoints go to the caller's addend images,
+  // beside the first frame's adjoint launch (walk_conv_adjoint_batch)
+  static_assert(SEP_ADDEND_MAX == JD_ADDEND_MAX, "the caller's addend images and the split's limit");
+  int addend_first = n_datasets;
+  if (addends && n_addends && n_comp == 1 && grad_flux && !accumulate && (reinterpret_cast<uintptr_t>(grad_flux[0]) & 15) == 0) {
+    addend_first = sep_addend_split(n_datasets, table, p->H, p->W, p->kh, p->kw, p->oy, p->ox);
+    for (int d = addend_first; d < n_datasets; ++d) {
+      float* image = addends[d - addend_first];
+      if (!image || (reinterpret_cast<uintptr_t>(image) & 15) != 0) {
+        addend_first = n_datasets;  // (fewer images than late datasets: the one-image adjoint)
+        break;
+      }
+    }
+    for (int d = addend_first; d < n_datasets; ++d) table.addend[d] = addends[d - addend_first];
+    if (addend_first < n_datasets && stream2 && stream2 != stream)
+      for (hipEvent_t& e : p->addend_events)
+        if (!e) JD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
   // a session passes the same pointers every step: look the table up by content, upload only a new one
   int slot = -1, victim = 0;
   for (int i = 0; i < jd_conv_plan::N_TABLES; ++i) {
@@ -806,7 +830,7 @@ extern "C" int jd_npred_poisson_batch_multi_fwd_bwd(jd_conv_plan* p, int n_datas
   SepBatchTable* const table_dev = p->table_dev[slot];
   const double n_pix = (double)p->H * (double)p->W;
   int n_part = 0;  // partial sums per dataset the forward launch wrote (<= tiles)
-  if (n_comp == 1 && grad_flux) {
+  if (n_comp == 1 && grad_flux && addend_first == n_datasets) {
     // one launch for the whole likelihood step where the strip-walk kernels apply (the g images are never written)
     int rc = walk_joint_step(n_datasets, flux[0], table, table_dev, grad_flux[0], p->H, p->W, p->kh, p->kw, p->oy, p->ox,
                              p->partials_batch, eps, (float)(1.0 / n_pix), grad_scale, accumulate, &n_part, s);
@@ -821,8 +845,10 @@ extern "C" int jd_npred_poisson_batch_multi_fwd_bwd(jd_conv_plan* p, int n_datas
   if (!grad_flux) return launch_finalize_rows(p->partials_batch, n_part, n_datasets, 1.0 / n_pix, stirling_mean, loss_out, s);
   int folded = 0;
   // all components in one adjoint launch where the strip-walk kernels apply (several components, or 9-16 datasets)
-  rc = walk_conv_adjoint_batch_all(n_datasets, n_comp, table, table_dev, grad_flux, p->H, p->W, p->kh, p->kw, p->oy, p->ox,
-                                   grad_scale, accumulate, s, p->partials_batch, 1.0 / n_pix, n_part, &folded);
+  rc = addend_first < n_datasets
+           ? JD_WALK_NOT_TAKEN
+           : walk_conv_adjoint_batch_all(n_datasets, n_comp, table, table_dev, grad_flux, p->H, p->W, p->kh, p->kw, p->oy,
+                                         p->ox, grad_scale, accumulate, s, p->partials_batch, 1.0 / n_pix, n_part, &folded);
   if (rc != JD_WALK_NOT_TAKEN) {
     if (rc || folded) return rc;
     return launch_finalize_rows(p->partials_batch, n_part, n_datasets, 1.0 / n_pix, stirling_mean, loss_out, s);
@@ -832,12 +858,39 @@ extern "C" int jd_npred_poisson_batch_multi_fwd_bwd(jd_conv_plan* p, int n_datas
     if ((rc = launch_sep_conv_adjoint_batch(n_datasets, n_comp, c, table, table_dev, grad_flux[c], p->H, p->W, p->kh,
                                             p->kw, p->oy, p->ox, grad_scale, accumulate, s,
                                             c == 0 && n_datasets <= 8 ? p->partials_batch : nullptr, 1.0 / n_pix, n_part,
-                                            &done)))
+                                            &done, addend_first < n_datasets ? addend_first : -1, as_stream(stream2),
+                                            p->addend_events)))
       return rc;
     folded |= done;
   }
+  if (n_addends) *n_addends = n_datasets - addend_first;
   if (!folded) return launch_finalize_rows(p->partials_batch, n_part, n_datasets, 1.0 / n_pix, stirling_mean, loss_out, s);
   return JD_OK;
+}
+
+extern "C" int jd_npred_poisson_batch_multi_fwd_bwd(jd_conv_plan* p, int n_datasets, int n_comp, const float* const* flux,
+                                                    const float* const* exposure, const float* const* khat,
+                                                    const float* const* background, const float* const* counts,
+                                                    const float* stirling_mean, float eps, float* const* loss_out,
+                                                    float* const* grad_flux, int accumulate, float grad_scale,
+                                                    void* stream) {
+  return npred_poisson_batch_impl("jd_npred_poisson_batch_multi_fwd_bwd", p, n_datasets, n_comp, flux, exposure, khat, background,
+                                  counts, stirling_mean, eps, loss_out, grad_flux, accumulate, grad_scale, stream, nullptr,
+                                  nullptr, nullptr);
+}
+
+extern "C" int jd_npred_poisson_batch_addends_fwd_bwd(jd_conv_plan* p, int n_datasets, const float* flux,
+                                                      const float* const* exposure, const float* const* khat,
+                                                      const float* const* background, const float* const* counts,
+                                                      const float* stirling_mean, float eps, float* const* loss_out,
+                                                      float* grad_flux, int accumulate, float grad_scale,
+                                                      float* const* addends, void* stream2, int* n_addends, void* stream) {
+  const char* who = "jd_npred_poisson_batch_addends_fwd_bwd";
+  JD_REQUIRE(flux && grad_flux && n_addends, "%s: null argument", who);
+  const float* fluxes[1] = {flux};
+  float* grads[1] = {grad_flux};
+  return npred_poisson_batch_impl(who, p, n_datasets, 1, fluxes, exposure, khat, background, counts, stirling_mean, eps, loss_out,
+                                  grads, accumulate, grad_scale, stream, addends, stream2, n_addends);
 }
 
 extern "C" int jd_npred_poisson_batch_fwd_bwd(jd_conv_plan* p, int n_datasets, const float* flux,

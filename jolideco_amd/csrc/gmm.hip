@@ -377,6 +377,7 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
     ga.preload = opt_value(OPT_GMM_GATHER_PRELOAD, 1) != 0;
     ga.vec = ga.vec && aligned(step->theta) && aligned(step->flux_in) && aligned(step->flux_out) && aligned(step->m) &&
              aligned(step->v) && aligned(step->mask);
+    for (int k = 0; k < ADDEND_MAX; ++k) ga.vec = ga.vec && aligned(step->addend[k]);
   }
   return launch_gather(ga, s);
 }
@@ -424,6 +425,11 @@ extern "C" int jd_gmm_prior_fwd_bwd_step(jd_gmm* g, const float* flux, int H, in
   a.step_size = step->step_size, a.beta1 = step->beta1, a.beta2 = step->beta2, a.one_minus_beta1 = step->one_minus_beta1;
   a.one_minus_beta2 = step->one_minus_beta2, a.bias2_sqrt = step->bias2_sqrt, a.eps = step->eps, a.lr = step->lr;
   a.zero_grad = 0, a.sgd = step->sgd ? 1 : 0, a.linear = step->use_log_flux ? 0 : 1, a.bias_dev = step->bias_dev;
+  static_assert(ADDEND_MAX == JD_ADDEND_MAX, "jd_step::addend and AdamArgs::addend");
+  for (int k = 0, live = 1; k < ADDEND_MAX; ++k) {  // (the leading non-null entries count)
+    live = live && step->addend[k] != nullptr;
+    a.addend[k] = live ? step->addend[k] : nullptr;
+  }
   return gmm_prior_impl(g, flux, H, W, stride, shift_y, shift_x, 0, -1, marginalize, value_scale, value_out, accumulate_value,
                         grad_coef, nullptr, nullptr, nullptr, stream, &a, shift_dev, phases);
 }

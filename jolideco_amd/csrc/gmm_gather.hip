@@ -113,7 +113,9 @@ __global__ __launch_bounds__(256) void gmm_gather_kernel(GmmGatherArgs a) {
 // floor(38 / s) + 1 = 8, 7, 6.  Columns: the tile's first column is shift_x (mod 4), not aligned with the grid: 10.
 constexpr int GATHER_T = 32, GATHER_MAX_P = 9, GATHER_MAX_PX = GATHER_MAX_P + 1;
 
-template <bool NORM>
+// NA: addend images of the fused step (jd_adam.h: step.addend[0 .. NA) are set), added to the gradient it reads before the
+// prior's term -- streams of the step like the others, loaded with them
+template <bool NORM, int NA>
 __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
 #pragma clang fp contract(off)
   use_device_shift(a);
@@ -151,6 +153,9 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
   bool loaded = early;  // the step's streams of this thread are in its registers
   float4 pre_g = make_float4(0.f, 0.f, 0.f, 0.f), pre_t = pre_g, pre_f = pre_g, pre_m = pre_g, pre_v = pre_g;
   float4 pre_k = make_float4(1.f, 1.f, 1.f, 1.f);
+  float4 pre_a[NA ? NA : 1];
+#pragma unroll
+  for (int k = 0; k < (NA ? NA : 1); ++k) pre_a[k] = pre_g;
   auto load_step_streams = [&]() {
     const AdamArgs& st = a.step;
     const size_t idx = (size_t)wrap(Yt - a.shift_y, a.H) * a.W + wrap(Xt - a.shift_x, a.W);
@@ -158,6 +163,8 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
     pre_t = *reinterpret_cast<const float4*>(st.theta + idx), pre_f = *reinterpret_cast<const float4*>(st.flux_in + idx);
     if (!st.sgd) pre_m = *reinterpret_cast<const float4*>(st.m + idx), pre_v = *reinterpret_cast<const float4*>(st.v + idx);
     if (st.mask) pre_k = *reinterpret_cast<const float4*>(st.mask + idx);
+#pragma unroll
+    for (int k = 0; k < NA; ++k) pre_a[k] = *reinterpret_cast<const float4*>(st.addend[k] + idx);
   };
   if (touched) {
     const bool slots = a.winner && *a.flag != a.gen;
@@ -263,6 +270,8 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
       float m[4] = {m4.x, m4.y, m4.z, m4.w}, v[4] = {v4.x, v4.y, v4.z, v4.w};
       float mk[4] = {k4.x, k4.y, k4.z, k4.w};
 #pragma unroll
+      for (int k = 0; k < NA; ++k) g[0] += pre_a[k].x, g[1] += pre_a[k].y, g[2] += pre_a[k].z, g[3] += pre_a[k].w;
+#pragma unroll
       for (int i = 0; i < 4; ++i) {
         if (any[i]) g[i] += term[i];
         adam_pixel(th[i], f[i], m[i], v[i], g[i], mk[i], st);
@@ -291,6 +300,8 @@ __global__ __launch_bounds__(256) void gmm_gather_tile_kernel(GmmGatherArgs a) {
     if (a.do_step) {
       const AdamArgs& st = a.step;
       float g = st.grad_flux[idx];
+#pragma unroll
+      for (int k = 0; k < NA; ++k) g += st.addend[k][idx];
       if (any[i]) g += term[i];
       float th = st.theta[idx], f = st.flux_in[idx], m = st.sgd ? 0.f : st.m[idx], v = st.sgd ? 0.f : st.v[idx];
       const float mk = st.mask ? st.mask[idx] : 1.f;
@@ -418,6 +429,13 @@ __global__ __launch_bounds__(256) void add_rolled_bands_step_kernel(AddBandsArgs
   }
 }
 
+template <int NA>
+static void tile_launch(bool has_norm, dim3 grid, const GmmGatherArgs& ga, hipStream_t s) {
+  static_assert(NA <= ADDEND_MAX, "AdamArgs::addend");
+  if (has_norm) gmm_gather_tile_kernel<true, NA><<<grid, 256, 0, s>>>(ga);
+  else gmm_gather_tile_kernel<false, NA><<<grid, 256, 0, s>>>(ga);
+}
+
 int launch_gather(const GmmGatherArgs& ga, hipStream_t s) {
   const bool has_norm = ga.norm.kind != NORM_IDENTITY;
   ProfScope prof(JD_KERNEL_GMM_GATHER, s);
@@ -425,8 +443,15 @@ int launch_gather(const GmmGatherArgs& ga, hipStream_t s) {
   if (ga.stride >= 4 && opt_value(OPT_GMM_GATHER_TILED, 1) != 0) {
     // (x: the first tile starts up to 3 pixels left of the image so that the pixel groups are aligned un-rolled)
     dim3 grid((ga.W + 3 + GATHER_T - 1) / GATHER_T, (ga.y_end - ga.y_begin + GATHER_T - 1) / GATHER_T);
-    if (has_norm) gmm_gather_tile_kernel<true><<<grid, 256, 0, s>>>(ga);
-    else gmm_gather_tile_kernel<false><<<grid, 256, 0, s>>>(ga);
+    int na = 0;
+    while (ga.do_step && na < ADDEND_MAX && ga.step.addend[na]) ++na;
+    switch (na) {
+      case 0: tile_launch<0>(has_norm, grid, ga, s); break;
+      case 1: tile_launch<1>(has_norm, grid, ga, s); break;
+      case 2: tile_launch<2>(has_norm, grid, ga, s); break;
+      case 3: tile_launch<3>(has_norm, grid, ga, s); break;
+      default: tile_launch<4>(has_norm, grid, ga, s); break;
+    }
   } else {
     dim3 grid((ga.W + 255) / 256, ga.y_end - ga.y_begin);
     if (has_norm) gmm_gather_kernel<true><<<grid, 256, 0, s>>>(ga);

@@ -5,6 +5,8 @@
 
 namespace jd {
 
+constexpr int ADDEND_MAX = 4;  // JD_ADDEND_MAX of jolideco_hip.h
+
 struct AdamArgs {
   float* theta;
   const float* flux_in;
@@ -20,6 +22,10 @@ struct AdamArgs {
   // nullable, device [2] = {step_size, bias2_sqrt}: read instead of the two members above (use_device_bias) -- the step
   // count of a captured graph's optimizer step lives in device memory, its launch arguments never change
   const float* bias_dev;
+  // nullable, in order: images the step adds to the gradient it reads, g = grad_flux; g += addend[0]; g += addend[1] ... --
+  // the adjoints of a joint step's second PSF frame, left in images of their own by a launch that ran beside the first
+  // frame's (walk_conv_adjoint_batch): the additions that launch would have made into grad_flux, in the same order
+  const float* addend[ADDEND_MAX];
 };
 
 __device__ __forceinline__ void use_device_bias(AdamArgs& a) {

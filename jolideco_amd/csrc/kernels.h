@@ -93,7 +93,8 @@ enum JdOption {
   OPT_GMM_SCREEN_NO_LDS_CONSTS, OPT_GMM_SCREEN_DEBUG, OPT_GMM_SCREEN, OPT_GMM_FUSED_BWD,
   OPT_GMM_GATHER_TILED, OPT_GMM_LSE_SCREEN, OPT_SEP_JOINT, OPT_SEP_JOINT_ROWS, OPT_SEP_JOINT_CHUNK,
   OPT_SEP_WALK_ADJ_ALL, OPT_SEP_WALK_COST33, OPT_SEP_WALK_ROWS33, OPT_SEP_NO_TRIM, OPT_SEP_WALK_ADJ_ROWS33,
-  OPT_SEP_WALK_ADJ33, OPT_FFT_NATIVE, OPT_DIRECT_AUTO_ALL, OPT_FFT_BATCH, OPT_FFT_TINY, OPT_FFT_POOL_IO, OPT_GMM_SORT_BLOCKS, OPT_GMM_GATHER_PRELOAD, OPT_COUNT
+  OPT_SEP_WALK_ADJ33, OPT_FFT_NATIVE, OPT_DIRECT_AUTO_ALL, OPT_FFT_BATCH, OPT_FFT_TINY, OPT_FFT_POOL_IO, OPT_GMM_SORT_BLOCKS, OPT_GMM_GATHER_PRELOAD,
+  OPT_SEP_ADJ_ADDENDS, OPT_COUNT
 };
 bool opt_is_set(int id);
 int opt_value(int id, int unset_value);
@@ -180,7 +181,14 @@ struct SepBatchTable {
   // bit d * n_comp + c: the operator of (dataset d, component c) walks in the 33-tap frame (several components: the
   // waves of a block choose their frame by it)
   unsigned long long frame33;
+  // dataset d's addend image (walk_conv_adjoint_batch: the adjoints of the step's second frame, one image per dataset,
+  // written by a plain walk launch beside the first frame's adjoint launch); null where the step has none
+  float* addend[SEP_MAX_BATCH];
 };
+constexpr int SEP_ADDEND_MAX = 4;  // addend images of a step (= ADDEND_MAX of jd_adam.h, JD_ADDEND_MAX)
+// How a batched step with datasets of both frames may split its adjoint (sep_addend_split): the datasets [first, n) -- all of
+// the second frame, behind all of the first -- go to addend images.  first = n: no split.
+int sep_addend_split(int n, const SepBatchTable& table, int H, int W, int kh, int kw, int oy, int ox);
 void walk_batch_order(SepBatchTable& table, int n, int n_comp, int kh, int kw, int oy, int ox);
 // *n_partials <- partial sums written per dataset: partials[d * *n_partials + i]
 int launch_sep_conv_poisson_batch(int n, int n_comp, const float* const* flux, const SepBatchTable& table,
@@ -189,10 +197,14 @@ int launch_sep_conv_poisson_batch(int n, int n_comp, const float* const* flux, c
                                   hipStream_t stream);
 // fin_partials != nullptr: block d < n also turns the fin_count partial sums of dataset d into its loss (see
 // SepBatchTable); *fin_done <- whether the launch did (a launch that cannot leaves the losses to launch_finalize_rows)
+// addend_first < n (one component, table.addend[d] set for d >= addend_first, see sep_addend_split): those datasets' adjoints
+// go to their addend images, on stream2 (nullable: on `stream`) between a fork behind the work `stream` holds now and a
+// join before this call returns (fork_join: the caller's two events for that); grad receives the datasets in front of them only
 int launch_sep_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTable& table, const SepBatchTable* table_dev,
                                   float* grad, int H, int W, int kh, int kw, int oy, int ox, float coef, int accumulate,
                                   hipStream_t stream, const double* fin_partials = nullptr, double fin_scale = 0.0,
-                                  int fin_count = 0, int* fin_done = nullptr);
+                                  int fin_count = 0, int* fin_done = nullptr, int addend_first = -1,
+                                  hipStream_t stream2 = nullptr, const hipEvent_t* fork_join = nullptr);
 // true when the walk kernels take some but not all operators of a batch: the caller then runs the per-dataset calls
 // (the batched and the per-dataset step must choose the same kernel for every dataset to stay bit-identical)
 bool sep_batch_is_mixed(int n, int n_comp, const SepBatchTable& table, int H, int W, int kh, int kw, int oy, int ox);
@@ -226,7 +238,8 @@ int walk_conv_poisson_batch_multi(int n, int n_comp, const float* const* flux, c
                                   hipStream_t stream);
 int walk_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTable& table, const SepBatchTable* table_dev,
                             float* grad, int H, int W, int kh, int kw, int oy, int ox, float coef, int accumulate,
-                            hipStream_t stream, const double* fin_partials, double fin_scale, int fin_count, int* fin_done);
+                            hipStream_t stream, const double* fin_partials, double fin_scale, int fin_count, int* fin_done,
+                            int addend_first = -1, hipStream_t stream2 = nullptr, const hipEvent_t* fork_join = nullptr);
 // the same for ALL components of up to 16 datasets in ONE launch (grads[c] (+)= ...); JD_WALK_NOT_TAKEN where the
 // per-component launches above are the better (or the only) choice
 int walk_conv_adjoint_batch_all(int n, int n_comp, const SepBatchTable& table, const SepBatchTable* table_dev,

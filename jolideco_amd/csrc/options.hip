@@ -38,6 +38,8 @@ OptionSlot g_options[OPT_COUNT] = {
     {"JD_GMM_SORT_BLOCKS", {INT_MIN}},  // tuning: most blocks of the record sort's count / scatter launches (default: one
                                         // record segment per block up to max(2 CUs, 2^20 / K))
     {"JD_GMM_GATHER_PRELOAD", {INT_MIN}},  // 0: the gather kernel loads the optimizer step's streams behind its block barrier
+    {"JD_SEP_ADJ_ADDENDS", {INT_MIN}},  // 0: a joint step over both PSF frames adds every adjoint into the gradient image
+                                        // (jd_npred_poisson_batch_addends_fwd_bwd writes no addend image)
 };
 
 int parse(const char* text) {

@@ -758,7 +758,7 @@ int launch_sep_conv_poisson_batch(int n, int n_comp, const float* const* flux, c
 int launch_sep_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTable& table, const SepBatchTable* table_dev,
                                   float* grad, int H, int W, int kh, int kw, int oy, int ox, float coef, int accumulate,
                                   hipStream_t stream, const double* fin_partials, double fin_scale, int fin_count,
-                                  int* fin_done) {
+                                  int* fin_done, int addend_first, hipStream_t stream2, const hipEvent_t* fork_join) {
   int rc = check_batch(n, n_comp);
   if (rc) return rc;
   if (comp < 0 || comp >= n_comp) return fail(JD_ERR_INVALID, "separable batch: component %d not in [0, %d)", comp, n_comp);
@@ -766,12 +766,14 @@ int launch_sep_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTab
   {
     int folded = 0;
     rc = walk_conv_adjoint_batch(n, n_comp, comp, table, table_dev, grad, H, W, kh, kw, oy, ox, coef, accumulate, stream,
-                                 fin_partials, fin_scale, fin_count, &folded);
+                                 fin_partials, fin_scale, fin_count, &folded, addend_first, stream2, fork_join);
     if (rc != JD_WALK_NOT_TAKEN) {
       if (fin_done) *fin_done = folded;
       return rc;
     }
   }
+  // (sep_addend_split promised the caller a walk launch: the tile kernel below adds every dataset into the gradient image)
+  if (addend_first > 0 && addend_first < n) return fail(JD_ERR_INVALID, "separable batch: the addend split needs the strip-walk kernels");
   SepArgs a{};
   a.out = grad, a.H = H, a.W = W, a.coef = coef, a.accumulate = accumulate, a.n_batch = n, a.table = table_dev;
   a.n_comp = n_comp, a.comp = comp;

@@ -97,6 +97,8 @@ struct WalkArgs {
   int n_batch;                 // > 0: per-dataset pointers come from `table`
   const SepBatchTable* table;
   int d_base;                  // batched adjoint: first dataset of this launch (wave w = dataset d_base + w)
+  int order0;                  // plain launch over several datasets (their adjoints into table->addend[d]): position of its
+                               // first dataset in table->order
   int n_comp, comp;            // batched adjoint: components per dataset and the one of this launch (table entry d * n_comp + comp)
   const double* fin_partials;  // batched adjoint: blocks < fin_n finalise the losses of the forward launch
   double fin_scale;
@@ -229,7 +231,10 @@ __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int 
   const gcp out_scale = (gcp)(batch ? a.table->scale[slot] : a.out_scale);
   const gcp background = (gcp)(batch ? a.table->bkg[d] : a.background);
   const gcp counts = (gcp)(batch ? a.table->cnt[d] : a.counts);
-  const gp out = (gp)(POISSON && batch ? a.table->g[d] : XCHG && a.comp_blocks ? a.out_comp[comp] : a.out);
+  // (a plain launch over several datasets -- the addend launch of walk_conv_adjoint_batch -- writes per-dataset images)
+  const gp out = (gp)(POISSON && batch ? a.table->g[d]
+                      : XCHG && a.comp_blocks ? a.out_comp[comp]
+                      : !XCHG && !POISSON && batch ? a.table->addend[d] : a.out);
   const gp npred_out = (gp)a.npred_out;
 
   // taps -> SGPRs
@@ -554,7 +559,7 @@ __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int 
 
 template <int WKT, int C, int P, bool POISSON, bool IN_SCALE, int XG, int XWT = XW>
 __global__ __launch_bounds__(XG ? 64 * XWT : 64) void walk_kernel(WalkArgs a) {
-  walk_body<WKT, C, P, POISSON, IN_SCALE, XG, XWT>(a, (int)blockIdx.x, a.strips, a.tiles_y, a.rows, 0);
+  walk_body<WKT, C, P, POISSON, IN_SCALE, XG, XWT>(a, (int)blockIdx.x, a.strips, a.tiles_y, a.rows, POISSON ? 0 : a.order0);
 }
 
 // Batched forward launch over operators of both frames: the 17-tap datasets at C17 columns per lane, the 33-tap
@@ -1280,6 +1285,23 @@ bool sep_batch_is_mixed(int n, int n_comp, const SepBatchTable& table, int H, in
   return yes != 0 && yes != n * n_comp;
 }
 
+// A step over datasets of both frames, all of one frame in front of all of the other and at most SEP_ADDEND_MAX of the
+// second: the first dataset of the second frame (walk_conv_adjoint_batch can leave the adjoints from there on in addend
+// images).  n: no such split (one frame, interleaved frames, too many late datasets, not a walk case, option
+// JD_SEP_ADJ_ADDENDS = 0).
+int sep_addend_split(int n, const SepBatchTable& table, int H, int W, int kh, int kw, int oy, int ox) {
+  if (opt_value(OPT_SEP_ADJ_ADDENDS, 1) == 0 || n < 2 || n > SEP_MAX_BATCH || !walk_enabled(H, W, n)) return n;
+  int first = n, f0 = 0;
+  for (int d = 0; d < n; ++d) {
+    const int f = dataset_frame(table, d, d, kh, kw, oy, ox);
+    if (!f) return n;
+    if (d == 0) f0 = f;
+    if (first == n && f != f0) first = d;
+    if (first != n && f == f0) return n;  // (the first frame again: the dataset order is not frame order)
+  }
+  return n - first <= SEP_ADDEND_MAX ? first : n;
+}
+
 // out (+)= coef * out_scale * conv/corr_same(in * in_scale, psf)      [launch_sep_conv's contract]
 int walk_conv(const float* in, const float* in_scale, const float* op, float* out, const float* out_scale, int H, int W,
               int kh, int kw, int oy, int ox, int adjoint, float coef, int accumulate, hipStream_t stream) {
@@ -1478,7 +1500,8 @@ int walk_conv_poisson_batch_multi(int n, int n_comp, const float* const* flux, c
 // first launch also turn the fin_count partial sums of dataset d into its loss (*fin_done <- 1)
 int walk_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTable& table, const SepBatchTable* table_dev,
                             float* grad, int H, int W, int kh, int kw, int oy, int ox, float coef, int accumulate,
-                            hipStream_t stream, const double* fin_partials, double fin_scale, int fin_count, int* fin_done) {
+                            hipStream_t stream, const double* fin_partials, double fin_scale, int fin_count, int* fin_done,
+                            int addend_first, hipStream_t stream2, const hipEvent_t* fork_join) {
   *fin_done = 0;
   if (!walk_enabled(H, W, n * n_comp) || !aligned16(grad)) return JD_WALK_NOT_TAKEN;
   int frames[SEP_MAX_BATCH];
@@ -1499,10 +1522,73 @@ int walk_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTable& ta
   // 54 / 72 / 90 = 111 / 85 / 97 us.  The 33-tap frame: two columns per lane, two waves per SIMD.
   int rc = sep_guard_check(&a.guard);
   if (rc) return rc;
-  for (int d0 = 0; d0 < n;) {
+  // The adjoints of the datasets [addend_first, n) (the caller's sep_addend_split: one frame, at most SEP_ADDEND_MAX) go to
+  // images of their own, table.addend[d] = (coef * corr(g_d, psf_d)) * E_d -- the value the exchange path below adds into
+  // the gradient image -- by the plain walk: one wave per (dataset, tile), no exchange, no barrier, and no access to the
+  // gradient image, so the launch depends on the forward launch alone and runs on stream2 BESIDE the launch(es) of the
+  // datasets in front of it (fork behind the forward launch, join before this call returns: a captured epoch sees a
+  // closed branch).  Whoever consumes the gradient adds the addends in dataset order (jd_adam.h): the same additions.
+  int n_main = n;
+  hipEvent_t join = nullptr;
+  if (addend_first > 0 && addend_first < n) {
+    const int m = n - addend_first, frame = frames[addend_first];
+    if (n_comp != 1 || m > SEP_ADDEND_MAX || !table_dev) return fail(JD_ERR_INVALID, "walk_conv_adjoint_batch: not an addend split");
+    for (int d = addend_first; d < n; ++d)
+      if (frames[d] != frame || !table.addend[d] || !aligned16(table.addend[d]))
+        return fail(JD_ERR_INVALID, "walk_conv_adjoint_batch: not an addend split");
+    const bool beside = stream2 && stream2 != stream;
+    if (beside && !(fork_join && fork_join[0] && fork_join[1]))
+      return fail(JD_ERR_INVALID, "walk_conv_adjoint_batch: a second stream needs the caller's fork and join events");
+    const hipStream_t s2 = beside ? stream2 : stream;
+    WalkArgs b = a;
+    b.out = nullptr, b.n_batch = m, b.accumulate = 0;
+    b.order0 = frame == 33 ? table.n17 : 0;  // (table.order: the 17-tap datasets, then the 33-tap ones, in dataset order)
+    int C1, r1;
+    walk_shape(b, m, true, frame, &C1, &r1);
+    // Beside the main launch the tiles are sized for HALF of the wave slots walk_shape fills (taller tiles: fewer waves, and
+    // fewer warm-up rows -- 32 per tile in the 33-tap frame).  Measured inside the fit (tools/ab.py, 2048^2, 6 + 2 datasets,
+    // accumulating launches 591.6 us per step): 33-tap tiles of 40 / 76 / 112 / 148 / 220 rows = 579.0 / 574.3 / 577.6 /
+    // 576.8 / 589.4 us (1664 / 864 / 608 / 448 / 320 waves beside the 1344 of the 17-tap launch; 40 is walk_shape's own
+    // choice, 76 this rule's) -- profiles/adjoint_addends/sweep_rows33.txt.  One sweep at one shape (33-tap, two late
+    // datasets): for a late 17-tap frame and for other sizes the rule is unmeasured.
+    if (beside) {
+      const long half = (long)(7.25 * device_cus()) / 2;
+      const int ws = frame == 33 ? Frame<33>::WS : Frame<17>::WS;
+      while (r1 < 4096 && (long)((W + 64 * C1 - 1) / (64 * C1)) * ((H + r1 - 1) / r1) * m > half) r1 += ws;
+    }
+    const int orows1 = opt_value(frame == 33 ? OPT_SEP_WALK_ADJ_ROWS33 : OPT_SEP_WALK_ADJ_ROWS, 0);
+    if (orows1 >= 20 && orows1 <= 4096) r1 = orows1;  // (tuning: the adjoint tile height option of the launch's frame)
+    walk_tiles(b, C1, r1);
+    if (beside) {
+      JD_HIP(hipEventRecord(fork_join[0], stream));
+      JD_HIP(hipStreamWaitEvent(stream2, fork_join[0], 0));
+    }
+    rc = launch_walk<false, false>(b, frame, C1, m, s2);
+    if (beside) {
+      // (from here on the branch is joined whatever fails: a capture is never left with an open branch)
+      join = fork_join[1];
+      // (a record that fails leaves nothing to join with: the error goes to the caller, whose capture, if any, is lost)
+      const hipError_t e = hipEventRecord(join, s2);
+      if (e != hipSuccess) return rc ? rc : fail(JD_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(e));
+    }
+    if (rc) {
+      if (join) (void)hipStreamWaitEvent(stream, join, 0);
+      return rc;
+    }
+    n_main = addend_first;
+  }
+  // (the main stream goes on behind the addend launch however this function is left: no branch of a capture stays open)
+  struct JoinOnExit {
+    hipStream_t stream;
+    hipEvent_t event;
+    ~JoinOnExit() {
+      if (event) (void)hipStreamWaitEvent(stream, event, 0);
+    }
+  } join_on_exit{stream, join};
+  for (int d0 = 0; d0 < n_main;) {
     const int frame = frames[d0];
     int m = 1;
-    while (d0 + m < n && m < XW && frames[d0 + m] == frame) ++m;  // datasets (= waves) of this launch: its block shape follows
+    while (d0 + m < n_main && m < XW && frames[d0 + m] == frame) ++m;  // datasets (= waves) of this launch: its block shape follows
     if (frame == 33 && opt_value(OPT_SEP_WALK_ADJ33, 0) == 1) m = 1;  // (tuning: one plain accumulating launch per dataset)
     const int xg = m >= 6 ? 6 : m >= 3 ? 3 : 2;
     const bool wide = frame == 17 && m >= 6 && opt_value(OPT_SEP_WALK_ADJ_COLS, 4) != 2;

@@ -147,13 +147,16 @@ class PoissonLoss:
             )
         return cache[key]
 
-    def fwd_bwd_batch(self, indices, flux, loss_outs, grad=None, accumulate=False, grad_scale=1.0, flux_nonneg=False):
+    def fwd_bwd_batch(self, indices, flux, loss_outs, grad=None, accumulate=False, grad_scale=1.0, flux_nonneg=False,
+                      addends=None, side_stream=None):
         """Forward model + Poisson NLL (+ gradient, summed over the datasets in order) of the datasets `indices`
         in three launches (+ one adjoint launch per further component); requires `batchable(indices)`.
         ``flux`` / ``grad``: a tensor (one component) or lists with one tensor per component, in component order.
         ``flux_nonneg``: the caller guarantees flux >= 0 everywhere (exp(theta) [x mask]); together with
         `mergeable(indices)` the components are then evaluated as ONE flux image, their sum: one forward model and one
-        adjoint per dataset whatever the number of components (models/npred.py:241-261: no term is clipped)."""
+        adjoint per dataset whatever the number of components (models/npred.py:241-261: no term is clipped).
+        ``addends`` / ``side_stream`` (one component): see `ConvPlan.npred_poisson_batch_fwd_bwd`; returns the number of
+        addend images the library wrote (the gradient is then ``grad + addends[0] + ...``), 0 otherwise."""
         per_dataset = [list(self.npred_models_all[i].values()) for i in indices]
         single = torch.is_tensor(flux)
         if not single and len(flux) > 1 and flux_nonneg and not accumulate and self.mergeable(indices):
@@ -172,16 +175,17 @@ class PoissonLoss:
             )
             if grad is not None:
                 copy_image_to(grad[0], list(grad[1:]))
-            return
+            return 0
         exposures = [[m.exposure for m in models] for models in per_dataset]
         khats = [[m.khat for m in models] for models in per_dataset]
         if single:
             exposures, khats = [e[0] for e in exposures], [k[0] for k in khats]
-        per_dataset[0][0].plan.npred_poisson_batch_fwd_bwd(
+        return per_dataset[0][0].plan.npred_poisson_batch_fwd_bwd(
             flux=flux, exposures=exposures, khats=khats,
             backgrounds=[self.npred_models_all[i].background for i in indices],
             counts=[self.counts_all[i] for i in indices], stirlings=[self.stirling_all[i] for i in indices],
             loss_outs=loss_outs, grad=grad, accumulate=accumulate, grad_scale=grad_scale,
+            addends=addends if single else None, side_stream=side_stream,
         )
 
     @classmethod

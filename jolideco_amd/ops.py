@@ -283,7 +283,7 @@ class ConvPlan:
     MAX_BATCH_COMPONENTS = 4  # SEP_BATCH_MAX_COMP
 
     def npred_poisson_batch_fwd_bwd(self, flux, exposures, khats, backgrounds, counts, stirlings, loss_outs, grad=None,
-                                    accumulate=False, grad_scale=1.0, eps=POISSON_EPS):
+                                    accumulate=False, grad_scale=1.0, eps=POISSON_EPS, addends=None, side_stream=None):
         """All datasets of a joint step at once (separable plan shared by every dataset and component): one launch for
         the forward models + Poisson passes, one for the losses, one adjoint launch per flux component
         (jd_npred_poisson_batch_multi_fwd_bwd).  Same numbers as the per-dataset calls with ``accumulate`` from the
@@ -291,7 +291,12 @@ class ConvPlan:
 
         One component: ``flux`` / ``grad`` are tensors and ``exposures`` / ``khats`` lists of per-dataset tensors.
         Several components: ``flux`` / ``grad`` are lists of tensors and ``exposures[d]`` / ``khats[d]`` lists with one
-        tensor per component."""
+        tensor per component.
+
+        ``addends`` (one component, one call's worth of datasets): images the library MAY write the adjoints of the
+        datasets of the second PSF frame into, one image each, instead of adding them to ``grad`` -- on ``side_stream``
+        (a `torch.cuda.Stream`, optional) beside the adjoint launch of the first frame (jd_npred_poisson_batch_addends_fwd_bwd).
+        Returns how many of them it wrote: the caller owes ``grad + addends[0] + addends[1] ...`` (0: ``grad`` is complete)."""
         n = len(exposures)
         if not (len(khats) == len(backgrounds) == len(counts) == len(stirlings) == len(loss_outs) == n):
             raise ValueError("all per-dataset lists must have the same length")
@@ -309,6 +314,23 @@ class ConvPlan:
             raise ValueError("one gradient image per flux component")
         for f in fluxes:
             self._check_image(f, "flux")
+        if addends and single and grads is not None and n <= self.MAX_BATCH and not accumulate:
+            for image in addends:
+                self._check_image(image, "addend")
+            used = c_int(0)
+            images = list(addends)[: _hip.ADDEND_MAX]
+            images += [None] * (_hip.ADDEND_MAX - len(images))
+            stirling_arr = (c_float * n)(*[float(v) for v in stirlings])
+            check(
+                _hip.lib().jd_npred_poisson_batch_addends_fwd_bwd(
+                    self._handle, n, ptr(fluxes[0]), ptr_array([e[0] for e in exposures]), ptr_array([k[0] for k in khats]),
+                    ptr_array(backgrounds), ptr_array(counts), stirling_arr, c_float(eps), ptr_array(loss_outs), ptr(grads[0]),
+                    0, c_float(grad_scale), ptr_array(images),
+                    None if side_stream is None else c_void_p(side_stream.cuda_stream), ctypes.byref(used),
+                    stream_ptr(fluxes[0].device),
+                )
+            )
+            return used.value
         for start in range(0, n, self.MAX_BATCH):
             sl = slice(start, min(n, start + self.MAX_BATCH))
             m = sl.stop - sl.start
@@ -321,6 +343,7 @@ class ConvPlan:
                     int(accumulate or start > 0), c_float(grad_scale), stream_ptr(fluxes[0].device),
                 )
             )
+        return 0
 
     def npred_poisson_calibrated_batch_fwd_bwd(self, flux, exposures, khats, backgrounds, counts, stirlings, loss_outs,
                                                calibrations, upsampling=1, grad=None, accumulate=False, grad_scale=1.0,
