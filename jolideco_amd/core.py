@@ -472,6 +472,22 @@ def _adam_step_many(cfg, items, cache, bias_dev=None):
         ))
 
 
+def _step_parameters(cfg, items, cache, bias_dev=None):
+    """The optimizer step of the small parameter tensors `items` = [(parameter, state)]: calibration parameters, the source
+    vectors of a sparse component.  A parameter whose ``grad`` is None takes no step and its count stays (torch.optim skips
+    it: jolideco/core.py:197-204,229).  Adam: one launch for all of them (`_adam_step_many`; ``bias_dev``: the device bias
+    terms of a planned epoch).  SGD: `jd_sgd_step` with ``use_log_flux=0``, the plain update of a parameter vector."""
+    if cfg.optimizer_type == "adam":
+        return _adam_step_many(cfg, items, cache, bias_dev)
+    lr = cfg.optimizer_kwargs["lr"]
+    for p, st in items:
+        if p.grad is None:
+            continue
+        st["step"] += 1
+        data = p.data
+        check(_hip.lib().jd_sgd_step(ptr(data), ptr(data), ptr(data), ptr(p.grad), None, p.numel(), lr, 0, 0, stream_ptr(p.device)))
+
+
 class _CalibrationStepper:
     """The optimizer of ONE dataset's calibration parameters (a (1, 2) shift and a (1,) log background norm) on the
     library's step kernel: `jd_adam_step` / `jd_sgd_step` with ``use_log_flux=0`` is the plain `torch.optim.Adam` /
@@ -494,17 +510,7 @@ class _CalibrationStepper:
                 p.grad.zero_()
 
     def step(self, bias_dev=None):
-        lib, cfg = _hip.lib(), self.cfg
-        if cfg.optimizer_type == "adam":  # both parameters of the dataset in one launch
-            _adam_step_many(cfg, list(zip(self.params, self.state)), self.__dict__.setdefault("_arrays", {}), bias_dev)
-            return
-        lr = cfg.optimizer_kwargs["lr"]
-        for p, st in zip(self.params, self.state):
-            if p.grad is None:
-                continue
-            st["step"] += 1
-            data, n, stream = p.data, p.numel(), stream_ptr(p.device)
-            check(lib.jd_sgd_step(ptr(data), ptr(data), ptr(data), ptr(p.grad), None, n, lr, 0, 0, stream))
+        _step_parameters(self.cfg, list(zip(self.params, self.state)), self.__dict__.setdefault("_arrays", {}), bias_dev)
 
 
 class StepScalars:
@@ -823,38 +829,26 @@ class FitSession:
         if opt is not None:
             opt.zero_grad(set_to_none=True)
 
-    def _cal_step(self, li):
-        opt = self.cal_optimizers[li]
-        if opt is not None:
-            opt.step()
-
-    def _cal_step_all(self):
-        """The calibration steps of all local datasets (a joint step updates them together): with Adam ONE launch for every
-        parameter that has a gradient (jd_adam_step_multi: the update of `_CalibrationStepper.step`, each parameter with
-        its own step count); otherwise the per-dataset steps."""
-        steppers = [self.cal_optimizers[li] for _, li in self.local_idx if self.cal_optimizers[li] is not None]
-        if not steppers:
-            return
-        cfg = self.cfg
-        if cfg.optimizer_type != "adam":
-            for opt in steppers:
-                opt.step()
-            return
-        items = [(p, st) for opt in steppers for p, st in zip(opt.params, opt.state)]
-        _adam_step_many(cfg, items, self.__dict__.setdefault("_cal_step_cache", {}))
-
     def _prior_rows(self, prior, state):
         if self.joint and self.dist.sharded and prior.shardable:
             return self.dist.shard_range(prior.n_patch_rows(state.shape), self.prior_shares)
         return None
 
-    def _apply_step(self, states, stepped):
-        """The optimizer step of the components the prior's gather kernel has not stepped already.  The hook keeps its
-        two-argument form `(states, step)` for a replacement installed by a test (which also switches the fusion off)."""
-        if stepped:
-            self.cfg._optimizer_step(states, self.step, stepped)
-        else:
-            self.cfg._optimizer_step(states, self.step)
+    def _flux_step(self, stepped, bias=None):
+        """Optimizer step number ``self.step + 1`` of the components whose prior (or band sum) has not applied it already
+        (``stepped``); ``bias``: the device bias terms of a planned epoch.  The hook keeps its two-argument form
+        `(states, step)` for a replacement installed by a test (which also switches the fusion off)."""
+        self.step += 1
+        for st in self.states:
+            st.bias_dev = bias
+        try:
+            if stepped:
+                self.cfg._optimizer_step(self.states, self.step, stepped)
+            else:
+                self.cfg._optimizer_step(self.states, self.step)
+        finally:
+            for st in self.states:
+                st.bias_dev = None
 
     def _fuse_step(self, st, prior):
         """The prior of this component applies the optimizer step itself (`device_fwd_bwd_step`): single process (the
@@ -996,18 +990,27 @@ class FitSession:
             k += len(items)
         sc.upload(shifts_host, biases)
         return {"shifts": shifts, "flux_bias": flux_bias, "cal_bias": cal_bias, "cal_items": cal_items, "n_steps": n_flux,
-                "signature": tuple(len(items) for items in cal_items)}
+                "signature": tuple(len(items) for items in cal_items), "two_streams": True}
 
-    def _plan_by_value(self):
-        """The same plan with HOST scalars: the shifts as drawn (in evaluation order), no device slots -- the kernels take
-        them by value.  The single-process epochs of the default policy (device bound fits) run through `_enqueue_epoch`
-        with this plan: one launch sequence for both forms."""
-        drawing, _, n_flux, cal_groups, _ = self._plan_slots()
-        n_eval = 1 if self.joint else len(self.local_idx) + 1
-        shifts = [{ci: self.priors[ci].draw_shifts() for ci in drawing} for _ in range(n_eval)]
-        cal_items = [[(p, st) for opt in group for p, st in zip(opt.params, opt.state)] for group in cal_groups]
-        return {"shifts": shifts, "flux_bias": [None] * n_flux, "cal_bias": [None] * len(cal_groups), "cal_items": cal_items,
-                "n_steps": n_flux, "signature": ()}
+    def _plan_by_value(self, two_streams=False):
+        """The same plan with HOST scalars and no device slots -- the kernels take them by value.  ``shifts`` None: every
+        step (and the trace) draws its own when it begins (`_draw_shifts`).  Every epoch that is not planned runs through
+        `_enqueue_epoch` with this plan: one launch sequence for both forms.  ``two_streams``: the epoch may put the priors'
+        first phase on the side stream (`_overlap_active`) -- only `epoch` says so, for the epochs fit for a device plan."""
+        plans = self.__dict__.setdefault("_by_value_plans", {})  # (nothing in it changes from epoch to epoch: built once)
+        if two_streams not in plans:
+            _, _, n_flux, cal_groups, _ = self._plan_slots()
+            cal_items = [[(p, st) for opt in group for p, st in zip(opt.params, opt.state)] for group in cal_groups]
+            plans[two_streams] = {"shifts": None, "flux_bias": [None] * n_flux, "cal_bias": [None] * len(cal_groups),
+                                  "cal_items": cal_items, "n_steps": n_flux, "signature": (), "two_streams": two_streams}
+        return plans[two_streams]
+
+    def _draw_shifts(self):
+        """Host shifts of ONE round of prior evaluations (a step, or the trace), drawn now in component order: the
+        generators advance as in `_plan_epoch`, and while the step runs `last_shifts` of a prior is the step's draw (a
+        replaced `_optimizer_step` may read it).  Passed in, so that a prior run in two phases does not draw twice.  (Not
+        for a sharded joint step: there a rank draws for the priors it evaluates, in its order -- `_sharded_priors`.)"""
+        return {ci: self.priors[ci].draw_shifts() for ci in self._plan_slots()[0]}
 
     # ---- the second frame's adjoints beside the first's -----------------------------------------------------------------
     def _likelihood_addends(self, early):
@@ -1041,27 +1044,31 @@ class FitSession:
                 self._addend_stream = torch.cuda.Stream(device=st.grad.device)
         return self._addend_images or None
 
-    def _joint_likelihood(self, fluxes, grads, early=()):
-        """The batched likelihood call of a joint step (gradient OVERWRITTEN); the images part of the gradient was left in
-        are handed to the fused step that follows (`_step_args`).  ``early``: what `_start_priors` returned for the step."""
+    def _joint_likelihood(self, fluxes, grads, slots, early=()):
+        """The batched likelihood call of a joint step (gradient OVERWRITTEN, the losses to ``slots``); the images part of the
+        gradient was left in are handed to the fused step that follows (`_step_args`).  ``early``: what `_start_priors`
+        returned for the step."""
         n_c = self.n_c
         addends = self._likelihood_addends(early)
         beside = None if addends is None else self._addend_stream
         used = self.total_loss.poisson_loss.fwd_bwd_batch(
             [li for _, li in self.local_idx], fluxes if n_c > 1 else fluxes[0],
-            [self._slot(gslot) for gslot, _ in self.local_idx], grad=grads if n_c > 1 else grads[0], accumulate=False,
+            slots, grad=grads if n_c > 1 else grads[0], accumulate=False,
             flux_nonneg=self.flux_nonneg, addends=addends, side_stream=beside,
         )
         self.addends_used = used or 0
         self.states[0].addends = tuple(addends[: self.addends_used]) if self.addends_used else ()
 
     # ---- the prior beside the likelihood ------------------------------------------------------------------------------
-    def _overlap_active(self):
+    def _overlap_active(self, plan):
         """Phase 1 of a GMM prior (value + gradient rows: it reads the flux only) runs on a second stream while the main
-        stream runs the likelihood launches of the step; the streams join in front of the gather (+ optimizer step).  Not
-        while the kernel timers run (a kernel timed beside another one is not the kernel's time); JOLIDECO_PRIOR_OVERLAP=0:
-        one stream."""
-        return self.overlap_prior and self._side_stream is not None and not self.dist.sharded and not _hip.profile_active()
+        stream runs the likelihood launches of the step; the streams join in front of the gather (+ optimizer step).  THE
+        place that says who may use a second stream: only an epoch whose plan allows it (``plan["two_streams"]``: `epoch`
+        found it fit for a plan in device memory -- one process, the session's own step, not the first epoch), and not while
+        the kernel timers run (a kernel timed beside another one is not the kernel's time); JOLIDECO_PRIOR_OVERLAP=0: one
+        stream.  Every other epoch keeps one stream and, with nothing beside the likelihood, the accumulating adjoint
+        launches (`_likelihood_addends`)."""
+        return plan["two_streams"] and self.overlap_prior and self._side_stream is not None and not _hip.profile_active()
 
     def _prior_calls(self, coef, shifts, bias):
         """The prior evaluations of ONE optimizer step as callables `call(phases)` (3: the whole pass): [(ci, call, steps)],
@@ -1090,10 +1097,10 @@ class FitSession:
                 calls.append((ci, call, False))
         return calls
 
-    def _start_priors(self, calls):
+    def _start_priors(self, calls, plan):
         """Phase 1 of every prior that has one (at most one per GMM handle: a handle holds one pass at a time) on the side
         stream, behind everything the main stream has been given so far.  Returns the components started."""
-        if not self._overlap_active():
+        if not self._overlap_active(plan):
             return set()
         eligible, seen = [], set()
         for ci, call, _ in calls:
@@ -1133,6 +1140,18 @@ class FitSession:
             for _, st in items:
                 st["step"] += 1
 
+    def _host_state(self, plan):
+        """Snapshot of the host state enqueuing an epoch changes (what `_commit_replay` advances)."""
+        return (self.step, [st.cur for st in self.states], [[st["step"] for _, st in items] for items in plan["cal_items"]])
+
+    def _restore_host_state(self, plan, snapshot):
+        self.step = snapshot[0]
+        for st, cur in zip(self.states, snapshot[1]):
+            st.cur = cur
+        for items, values in zip(plan["cal_items"], snapshot[2]):
+            for (_, st), value in zip(items, values):
+                st["step"] = value
+
     def _epoch_planned(self):
         plan = self._plan_epoch()
         parity = tuple(st.cur for st in self.states) + plan["signature"]
@@ -1145,7 +1164,7 @@ class FitSession:
             self._commit_replay(plan)
         elif self.use_graph and self._epochs_done >= self.GRAPH_WARMUP and not _hip.profile_active():
             # capture this epoch's launches (nothing runs during the capture), then run them
-            snapshot = (self.step, [st.cur for st in self.states], [[st["step"] for _, st in items] for items in plan["cal_items"]])
+            snapshot = self._host_state(plan)
             graph = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(graph):
@@ -1155,12 +1174,7 @@ class FitSession:
                 # aborted enqueue changed is put back and the epoch runs eagerly)
                 log.warning("hipGraph capture of an epoch failed; continuing without graphs", exc_info=True)
                 self.use_graph = False
-                self.step = snapshot[0]
-                for st, cur in zip(self.states, snapshot[1]):
-                    st.cur = cur
-                for items, values in zip(plan["cal_items"], snapshot[2]):
-                    for (_, st), value in zip(items, values):
-                        st["step"] = value
+                self._restore_host_state(plan, snapshot)
                 torch.cuda.synchronize()
                 self._enqueue_epoch(plan)
             else:
@@ -1170,112 +1184,149 @@ class FitSession:
             self._enqueue_epoch(plan)
         self._epochs_done += 1
 
+    def _sharded_priors(self, coef):
+        """The priors and collectives of a SHARDED joint step, between its likelihood calls and its optimizer step.  The
+        element-wise priors (not shardable: rank 0 only, summed by the all-reduce) and, without a band plan, this rank's
+        patch rows of the others go into the flat buffer in front of its all-reduce.  With a band plan the all-reduce is
+        in flight while the rank's bands are evaluated; one all-gather carries them and their values to every rank, and
+        every rank adds them -- with the optimizer step where `_fuse_band_step` allows.  The priors draw their shifts here,
+        as they are evaluated.  Returns the components stepped."""
+        from .ops import add_rolled_bands, add_rolled_bands_step
+
+        cfg, dist, states, priors = self.cfg, self.dist, self.states, self.priors
+        n_d, slot = self.n_d, self._slot
+        banded = {item["ci"]: item for item in (self.band_plan or [])}
+        for ci, (st, prior) in enumerate(zip(states, priors)):
+            if ci in banded or getattr(prior, "value_is_zero", False):
+                continue  # (a uniform prior: `scalars.zero_()` has written its 0)
+            if not prior.shardable and dist.rank != 0:
+                continue
+            prior.device_fwd_bwd(st.flux_cur, slot(n_d + ci), grad=st.grad, coef=coef, patch_rows=self._prior_rows(prior, st))
+        stepped = set()
+        if not banded:
+            self._timed("all_reduce_blocking", lambda: dist.all_reduce_sum(self.comm))
+            return stepped
+        # likelihood gradient (+ element-wise priors, + dataset losses) on its way while the bands are evaluated
+        pending = dist.all_reduce_sum_async(self.comm)
+        for ci, item in banded.items():
+            prior = priors[ci]
+            prior.device_fwd_bwd(
+                states[ci].flux_cur, self.band_send[item["value"] : item["value"] + 1], coef=coef,
+                patch_rows=item["rows"], band_out=self.band_send[item["offset"] : item["offset"] + item["size"]],
+            )
+            item["shifts"] = prior.last_shifts
+        self._timed("all_gather_bands", lambda: dist.all_gather_flat(self.band_recv, self.band_send))
+        if pending is not None:
+            self._timed("all_reduce_wait", pending.wait)
+        pieces = self.band_recv.view(dist.world_size, self.band_chunk)
+        for ci, item in banded.items():
+            st, bands = states[ci], self.band_recv[item["offset"] :]
+            if self._fuse_band_step(st):
+                # the bands are the last term of this component's gradient: their sum and the optimizer step in one launch
+                # (the gradient image is read once, never written)
+                add_rolled_bands_step(st.grad.shape, item["shifts"], bands, self.band_chunk, item["y_ranges"],
+                                      cfg._step_args(st, self.step + 1))
+                stepped.add(ci)
+            else:
+                add_rolled_bands(st.grad, item["shifts"], bands, self.band_chunk, item["y_ranges"])
+            # every rank sums the shard values in rank order: identical replicas
+            if dist.dry_run:
+                slot(n_d + ci).copy_(pieces[dist.rank, item["value"] : item["value"] + 1])
+            else:
+                torch.sum(pieces[:, item["value"]], dim=0, keepdim=True, out=slot(n_d + ci))
+        return stepped
+
     def _enqueue_epoch(self, plan):
-        """The launches of one epoch of a single-process fit, reading the step scalars of `plan` from device memory: the
-        body of `_epoch_by_value` without its sharded branches (same kernels, same order, same results bit for bit)."""
+        """The launches of ONE epoch, the only place that spells them out: likelihood calls, prior calls, collectives,
+        optimizer step, calibration steps, the sequential mode's trace and the validation losses.  ``plan`` carries the
+        step scalars: device slots (`_plan_epoch`: the launch arguments never change, so the epoch can be captured) or
+        host values (`_plan_by_value`) -- same kernels, same order, same results bit for bit."""
         cfg, states, priors, total_loss = self.cfg, self.states, self.priors, self.total_loss
+        poisson, local = total_loss.poisson_loss, [li for _, li in self.local_idx]
         n_d, n_c = self.n_d, self.n_c
         slot = self._slot
+        slots = [slot(gslot) for gslot, _ in self.local_idx]
         beta = -float(cfg.beta)
+        cache = self.__dict__.setdefault("_cal_step_cache", {})
+        planned_shifts = plan["shifts"]
 
-        def flux_step(stepped, bias):
-            self.step += 1
-            for st in states:
-                st.bias_dev = bias
-            try:
-                self._apply_step(states, stepped)
-            finally:
-                for st in states:
-                    st.bias_dev = None
-
-        def cal_steps(items, bias):
-            if not items:
-                return
-            if cfg.optimizer_type != "adam":
-                lr = cfg.optimizer_kwargs["lr"]
-                for p, st in items:
-                    if p.grad is None:
-                        continue
-                    st["step"] += 1
-                    check(_hip.lib().jd_sgd_step(ptr(p.data), ptr(p.data), ptr(p.data), ptr(p.grad), None, p.numel(), lr, 0, 0,
-                                                 stream_ptr(p.device)))
-                return
-            _adam_step_many(cfg, items, self.__dict__.setdefault("_cal_step_cache", {}), bias)
+        def shifts_of(j):
+            return self._draw_shifts() if planned_shifts is None else planned_shifts[j]
 
         if self.joint:
+            # ---- one step on sum_d L_d - beta * logprior ----------------------------------------
+            sharded = self.dist.sharded
             fluxes = [st.flux_cur for st in states]
             grads = [st.grad for st in states]
-            calls = self._prior_calls(beta, plan["shifts"][0], plan["flux_bias"][0])
-            early = self._start_priors(calls)  # (the priors' first phase beside the likelihood launches below)
-            first = True
+            if sharded:
+                self.scalars.zero_()
+            calls = [] if sharded else self._prior_calls(beta, shifts_of(0), plan["flux_bias"][0])
+            early = self._start_priors(calls, plan)  # (the priors' first phase beside the likelihood launches below)
             if self.batch_joint:
-                self._joint_likelihood(fluxes, grads, early)
-                first = False
+                # all local datasets in three launches (forward + Poisson, losses, adjoint): same numbers as the loop
+                self._joint_likelihood(fluxes, grads, slots, early)
             elif self.batch_joint_calibrated:
-                for _, li in self.local_idx:
+                for li in local:
                     self._cal_zero_grad(li)
-                total_loss.poisson_loss.fwd_bwd_batch_calibrated(
-                    [li for _, li in self.local_idx], fluxes[0], [slot(gslot) for gslot, _ in self.local_idx], grad=grads[0],
-                    accumulate=False,
-                )
-                first = False
+                poisson.fwd_bwd_batch_calibrated(local, fluxes[0], slots, grad=grads[0], accumulate=False)
             else:
-                for gslot, li in self.local_idx:
+                for k, li in enumerate(local):
                     self._cal_zero_grad(li)
-                    total_loss.poisson_loss.fwd_bwd(li, fluxes, slot(gslot), grads=grads, accumulate=not first,
-                                                    flux_nonneg=self.flux_nonneg)
-                    first = False
-            if first:
-                for g in grads:
-                    g.zero_()
-            flux_step(self._finish_priors(calls, early), plan["flux_bias"][0])
-            cal_steps(plan["cal_items"][0], plan["cal_bias"][0])
+                    poisson.fwd_bwd(li, fluxes, slots[k], grads=grads, accumulate=k > 0, flux_nonneg=self.flux_nonneg)
+                if not local:
+                    for g in grads:
+                        g.zero_()
+            self._flux_step(self._sharded_priors(beta) if sharded else self._finish_priors(calls, early), plan["flux_bias"][0])
+            if plan["cal_items"][0]:
+                _step_parameters(cfg, plan["cal_items"][0], cache, plan["cal_bias"][0])
         else:
+            # ---- the reference loop: one step per dataset (core.py:214-229) -----------------------
             coef = beta / total_loss.prior_weight
-            for j, (gslot, li) in enumerate(self.local_idx):
+            for j, li in enumerate(local):
                 fluxes = [st.flux_cur for st in states]
                 grads = [st.grad for st in states]
-                calls = self._prior_calls(coef, plan["shifts"][j], plan["flux_bias"][j])
-                early = self._start_priors(calls)
+                calls = self._prior_calls(coef, shifts_of(j), plan["flux_bias"][j])
+                early = self._start_priors(calls, plan)
                 self._cal_zero_grad(li)
-                total_loss.poisson_loss.fwd_bwd(li, fluxes, slot(gslot), grads=grads, accumulate=False,
-                                                flux_nonneg=self.flux_nonneg)
-                flux_step(self._finish_priors(calls, early), plan["flux_bias"][j])
-                cal_steps(plan["cal_items"][j], plan["cal_bias"][j])
+                poisson.fwd_bwd(li, fluxes, slots[j], grads=grads, accumulate=False, flux_nonneg=self.flux_nonneg)
+                self._flux_step(self._finish_priors(calls, early), plan["flux_bias"][j])
+                if plan["cal_items"][j]:
+                    _step_parameters(cfg, plan["cal_items"][j], cache, plan["cal_bias"][j])
+            # ---- trace on the STALE fluxes of the last step (core.py:247) -------------------------
             stale = [st.flux_trace for st in states]
             if self.batch_trace:
-                total_loss.poisson_loss.fwd_bwd_batch(
-                    [li for _, li in self.local_idx], stale if n_c > 1 else stale[0],
-                    [slot(gslot) for gslot, _ in self.local_idx], flux_nonneg=self.flux_nonneg,
-                )
+                poisson.fwd_bwd_batch(local, stale if n_c > 1 else stale[0], slots, flux_nonneg=self.flux_nonneg)
             else:
-                for gslot, li in self.local_idx:
-                    total_loss.poisson_loss.fwd_bwd(li, stale, slot(gslot), flux_nonneg=self.flux_nonneg)
-            trace_shifts = plan["shifts"][-1]
+                for k, li in enumerate(local):
+                    poisson.fwd_bwd(li, stale, slots[k], flux_nonneg=self.flux_nonneg)
+            trace_shifts = shifts_of(-1)
             for ci, (st, prior) in enumerate(zip(states, priors)):
                 if getattr(prior, "value_is_zero", False):
                     continue
                 kwargs = {"shifts": trace_shifts[ci]} if ci in trace_shifts else {}
                 prior.device_fwd_bwd(st.flux_trace, slot(n_d + ci), **kwargs)
+        if self.n_val:
+            # validation losses on the same fluxes the trace row refers to
+            vfl = [st.flux_prev if self.joint else st.flux_trace for st in states]
+            for vi in range(self.n_val):
+                total_loss.poisson_loss_validation.fwd_bwd(vi, vfl, slot(n_d + n_c + vi))
 
     def epoch(self):
         """One epoch of the fit, enqueued without any host synchronisation: planned (device-resident step scalars, replayed
-        from a captured hipGraph once warm) where `_planned_capable` holds, else the by-value form."""
+        from a captured hipGraph once warm) where `_planned_capable` holds, else the same launches with host scalars."""
         if getattr(self, "_option_generation", None) != _hip.OPTION_GENERATION:
             self.reset_graphs()
-        # (the first epoch runs by value: it shows which calibration parameters receive a gradient at all)
-        if self._total_epochs > 0 and self._planned_capable() and not _hip.profile_active():
-            if self.graph_mode != "auto" or self.use_graph:
-                self._total_epochs += 1
-                return self._epoch_planned()
-            if self.graph_policy == "undecided":
-                return self._epoch_probe()
-            self._total_epochs += 1
-            return self._enqueue_epoch(self._plan_by_value())
+        # (the first epoch runs with host scalars: it shows which calibration parameters receive a gradient at all)
+        planned = self._total_epochs > 0 and self._planned_capable() and not _hip.profile_active()
         self._total_epochs += 1
-        if self._graphs:
-            self.reset_graphs()
-        return self._epoch_by_value()
+        if not planned:
+            if self._graphs:
+                self.reset_graphs()
+        elif self.graph_mode != "auto" or self.use_graph:
+            return self._epoch_planned()
+        elif self.graph_policy == "undecided":
+            return self._epoch_probe()
+        return self._enqueue_epoch(self._plan_by_value(two_streams=planned))
 
     AUTO_PROBE = 8  # by-value epochs timed before the "auto" policy decides
     AUTO_CLEAR = 0.4  # host enqueue time / device time of an epoch below which the device bounds the fit for certain
@@ -1297,10 +1348,9 @@ class FitSession:
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
         t0 = time.perf_counter()
-        self._enqueue_epoch(self._plan_by_value())
+        self._enqueue_epoch(self._plan_by_value(two_streams=True))
         host = time.perf_counter() - t0
         end.record()
-        self._total_epochs += 1
         self._probe.append((host, start, end))
         if len(self._probe) < self.AUTO_PROBE * (2 if two_forms else 1):
             return
@@ -1370,130 +1420,6 @@ class FitSession:
             self._graphs = {}
             self.overlap_prior = trial["by_value_form"]
             self.graph_policy = f"by value (measured: {numbers})"
-
-    def _epoch_by_value(self):
-        cfg, dist, states, priors, total_loss = self.cfg, self.dist, self.states, self.priors, self.total_loss
-        n_d, n_c = self.n_d, self.n_c
-        slot = self._slot
-        if self.joint:
-            # ---- one step on sum_d L_d - beta * logprior ------------------------------------
-            fluxes = [st.flux_cur for st in states]
-            grads = [st.grad for st in states]
-            if dist.sharded:
-                self.scalars.zero_()
-            first = True
-            if self.batch_joint:
-                # all local datasets in three launches (forward + Poisson, losses, adjoint): same numbers as the loop
-                self._joint_likelihood(fluxes, grads)
-                first = False
-            elif self.batch_joint_calibrated:
-                for _, li in self.local_idx:
-                    self._cal_zero_grad(li)
-                total_loss.poisson_loss.fwd_bwd_batch_calibrated(
-                    [li for _, li in self.local_idx], fluxes[0], [slot(gslot) for gslot, _ in self.local_idx], grad=grads[0],
-                    accumulate=False,
-                )
-                first = False
-            else:
-                for gslot, li in self.local_idx:
-                    self._cal_zero_grad(li)
-                    total_loss.poisson_loss.fwd_bwd(li, fluxes, slot(gslot), grads=grads, accumulate=not first,
-                                                    flux_nonneg=self.flux_nonneg)
-                    first = False
-            if first:
-                for g in grads:
-                    g.zero_()
-            banded = {item["ci"]: item for item in (self.band_plan or [])}
-            stepped = set()
-            for ci, (st, prior) in enumerate(zip(states, priors)):
-                if ci in banded:
-                    continue
-                if dist.sharded and not prior.shardable and dist.rank != 0:
-                    continue  # cheap element-wise priors: rank 0 only, summed by the all-reduce
-                if self._fuse_step(st, prior):
-                    # single process: the prior is the last gradient term of its component -- its gather kernel applies
-                    # the optimizer step (one pass over the gradient image and one launch less)
-                    prior.device_fwd_bwd_step(st.flux_cur, slot(n_d + ci), -float(cfg.beta), cfg._step_args(st, self.step + 1))
-                    stepped.add(ci)
-                    continue
-                prior.device_fwd_bwd(
-                    st.flux_cur, slot(n_d + ci), grad=st.grad, coef=-float(cfg.beta),
-                    patch_rows=self._prior_rows(prior, st),
-                )
-            if banded:
-                # likelihood gradient (+ element-wise priors, + dataset losses) on its way while the prior is evaluated
-                from .ops import add_rolled_bands
-
-                pending = dist.all_reduce_sum_async(self.comm)
-                for ci, item in banded.items():
-                    st, prior = states[ci], priors[ci]
-                    prior.device_fwd_bwd(
-                        st.flux_cur, self.band_send[item["value"] : item["value"] + 1], coef=-float(cfg.beta),
-                        patch_rows=item["rows"], band_out=self.band_send[item["offset"] : item["offset"] + item["size"]],
-                    )
-                    item["shifts"] = prior.last_shifts
-                self._timed("all_gather_bands", lambda: dist.all_gather_flat(self.band_recv, self.band_send))
-                if pending is not None:
-                    self._timed("all_reduce_wait", pending.wait)
-                pieces = self.band_recv.view(dist.world_size, self.band_chunk)
-                for ci, item in banded.items():
-                    if self._fuse_band_step(states[ci]):
-                        # the bands are the last term of this component's gradient: their sum and the optimizer step in
-                        # one launch (the gradient image is read once, never written)
-                        from .ops import add_rolled_bands_step
-
-                        add_rolled_bands_step(states[ci].grad.shape, item["shifts"], self.band_recv[item["offset"] :],
-                                              self.band_chunk, item["y_ranges"], cfg._step_args(states[ci], self.step + 1))
-                        stepped.add(ci)
-                    else:
-                        add_rolled_bands(states[ci].grad, item["shifts"], self.band_recv[item["offset"] :], self.band_chunk,
-                                         item["y_ranges"])
-                    # every rank sums the shard values in rank order: identical replicas
-                    if dist.dry_run:
-                        slot(n_d + ci).copy_(pieces[dist.rank, item["value"] : item["value"] + 1])
-                    else:
-                        torch.sum(pieces[:, item["value"]], dim=0, keepdim=True, out=slot(n_d + ci))
-            elif dist.sharded:
-                self._timed("all_reduce_blocking", lambda: dist.all_reduce_sum(self.comm))
-            self.step += 1
-            self._apply_step(states, stepped)
-            self._cal_step_all()
-        else:
-            # ---- the reference loop: one step per dataset (core.py:214-229) -------------------
-            for gslot, li in self.local_idx:
-                fluxes = [st.flux_cur for st in states]
-                grads = [st.grad for st in states]
-                self._cal_zero_grad(li)
-                total_loss.poisson_loss.fwd_bwd(li, fluxes, slot(gslot), grads=grads, accumulate=False,
-                                                flux_nonneg=self.flux_nonneg)
-                coef = -float(cfg.beta) / total_loss.prior_weight
-                stepped = set()
-                for ci, (st, prior) in enumerate(zip(states, priors)):
-                    if self._fuse_step(st, prior):
-                        prior.device_fwd_bwd_step(st.flux_cur, slot(n_d + ci), coef, cfg._step_args(st, self.step + 1))
-                        stepped.add(ci)
-                    else:
-                        prior.device_fwd_bwd(st.flux_cur, slot(n_d + ci), grad=st.grad, coef=coef)
-                self.step += 1
-                self._apply_step(states, stepped)
-                self._cal_step(li)
-            # ---- trace on the STALE fluxes of the last step (core.py:247) ---------------------
-            stale = [st.flux_trace for st in states]
-            if self.batch_trace:
-                total_loss.poisson_loss.fwd_bwd_batch(
-                    [li for _, li in self.local_idx], stale if n_c > 1 else stale[0],
-                    [slot(gslot) for gslot, _ in self.local_idx], flux_nonneg=self.flux_nonneg,
-                )
-            else:
-                for gslot, li in self.local_idx:
-                    total_loss.poisson_loss.fwd_bwd(li, stale, slot(gslot), flux_nonneg=self.flux_nonneg)
-            for ci, (st, prior) in enumerate(zip(states, priors)):
-                prior.device_fwd_bwd(st.flux_trace, slot(n_d + ci))
-        if self.n_val:
-            # validation losses on the same fluxes the trace row refers to
-            vfl = [st.flux_prev if self.joint else st.flux_trace for st in states]
-            for vi in range(self.n_val):
-                total_loss.poisson_loss_validation.fwd_bwd(vi, vfl, slot(n_d + n_c + vi))
 
 
 class MAPDeconvolverResult:
