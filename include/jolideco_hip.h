@@ -310,7 +310,8 @@ int jd_conv_same_adjoint(jd_conv_plan* plan, const float* grad_out, const float*
  *                              and the whole pass only (phases = 3); argmax_out, shift_dev, marginalize, accumulate_value and
  *                              the handle's image norm as for D = 64; patch size 16, stride in [1, 16], H, W >= 16;
  *   jd_gmm_estimate_log_prob   x: (n, 256);
- *   jd_gmm_set_image_norm, jd_gmm_is_triangular, jd_gmm_screen_stats (no screened pass: generation 0), jd_gmm_destroy as for D = 64;
+ *   jd_gmm_set_image_norm, jd_gmm_set_patch_norm, jd_gmm_is_triangular, jd_gmm_screen_stats (no screened pass: generation 0),
+ *   jd_gmm_destroy as for D = 64;
  *   a patch row shard, phases 1 / 2, jd_gmm_prior_fwd_bwd_step, jd_gmm_prior_band_fwd_bwd and jd_gmm_screen_clock return
  *   JD_ERR_INVALID with a message that names D = 256 and the refused option; nothing is launched and the handle stays
  *   usable.  No D = 256 call ever reaches a D = 64 kernel.
@@ -344,6 +345,33 @@ typedef struct {
   float p0, p1;
 } jd_image_norm;
 int jd_gmm_set_image_norm(jd_gmm* gmm, const jd_image_norm* norm);
+
+/* PATCH NORM of the prior (jolideco/utils/norms.py:97-112; priors/patches/core.py:218 `patches = self.patch_norm(...)`):
+ * what the three jd_gmm_prior_* calls below make of a patch p of the (normed, rolled) image that passed the `> -1e5` filter
+ * before the mixture sees it, m = mean(p) over its D pixels:
+ *   kind 0 subtract-mean       x = p - m                  (the state of a new handle)
+ *        1 std-subtract-mean   x = (p - m) / m            (a float32 subtraction, then a correctly rounded division)
+ * Everything behind x is the same; the gradient rows carry the norm's adjoint, kind 1:
+ * dv/dp_j = (gamma_j - mean(gamma) - (gamma . x) / D) / m with gamma = dv/dx.  m = 0 gives inf / NaN as in the
+ * reference (no guard).  Kind 1 always takes the dense fp32 kernels: the fp16 screen, the screened logsumexp and the
+ * fused exact stage are never used for it, whatever JD_GMM_SCREEN / JD_GMM_LSE_SCREEN say (their error bounds are those
+ * of mean-free patches), and jd_gmm_screen_stats' generation does not advance.  Phases, the patch row shard, the band
+ * output and jd_gmm_prior_fwd_bwd_step work as for kind 0 (D = 64); D = 256 handles accept both kinds.
+ * jd_gmm_estimate_log_prob takes finished patches and applies no norm.
+ * Like the image norm it is a state of the HANDLE, taken by the next jd_gmm_prior_* call: callers that share a handle
+ * between priors set it in front of every call.  A phase-2 call must find the patch norm of its phase 1 (JD_ERR_INVALID
+ * otherwise).  Any other kind returns JD_ERR_INVALID and leaves the handle as it was. */
+int jd_gmm_set_patch_norm(jd_gmm* gmm, int kind);
+/* RESIDUAL OF THE CONSTANTS.  const_k of jd_gmm_create is a float32 number per component, and the caller sums its three
+ * terms in float32 as the reference does: an error of up to a few 1e-5 that every patch choosing the component shares.
+ * Under the subtract-mean norm a patch's value is of the order of -1e4 and that is 1e-9 of it.  Standardized patches are
+ * of order 0.1: the value is c_k - q_k / 2 with both terms several times its size, and the same error is a few 1e-6 of
+ * the prior value.  residual: HOST pointer to K floats, residual[k] = (c_k evaluated in float64) - (double)const_k[k].
+ * The passes of patch norm kind 1 form l_k = fmaf(-0.5, q_k, const_k[k]) + residual[k] (value, arg-max and
+ * responsibilities alike); the passes of kind 0, the screen and jd_gmm_estimate_log_prob never read it, so setting it
+ * changes no bit of theirs.  A new handle holds zeros.  A property of the mixture, not of a pass: set it once after
+ * jd_gmm_create (the call synchronises the device).  D = 256 handles accept it.  Non-finite entries: JD_ERR_INVALID. */
+int jd_gmm_set_const_residual(jd_gmm* gmm, const float* residual);
 
 /* log-prior value and gradient of GMMPatchPrior.__call__ (priors/patches/core.py:189-246) with
  * IdentityImageNorm, SubtractMeanPatchNorm (utils/norms.py:97-103), cycle-spin roll by

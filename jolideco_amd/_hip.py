@@ -84,6 +84,8 @@ EXPORTS = {
     "jd_gmm_destroy": (c_int, [c_void_p]),
     "jd_gmm_is_triangular": (c_int, [c_void_p]),
     "jd_gmm_set_image_norm": (c_int, [c_void_p, c_void_p]),
+    "jd_gmm_set_patch_norm": (c_int, [c_void_p, c_int]),
+    "jd_gmm_set_const_residual": (c_int, [c_void_p, fp]),
     "jd_gmm_prior_fwd_bwd": (
         c_int,
         [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int,

@@ -593,6 +593,11 @@ class FitSession:
             raise NotImplementedError(
                 f"compute_error=True with the sparse flux component {sparse[0]!r} is not implemented in jolideco_amd"
             )
+        if deconvolver.compute_error:
+            for c in components.values():  # (a GMM prior under the standardized patch norm names itself and raises)
+                check = getattr(getattr(c, "prior", None), "check_hessian_ones", None)
+                if check is not None:
+                    check()
         if sparse and deconvolver.checkpoint_path is not None:
             raise NotImplementedError(
                 f"checkpoints are ASDF files, which cannot carry the sparse flux component {sparse[0]!r}: fit without "

@@ -125,8 +125,9 @@ extern "C" int jd_gmm_create(int K, int Dn, const float* prec_chol, const float*
   };
   int rc;
   if ((rc = upload(g->dense.afrag, afrag.data(), afrag.size())) || (rc = upload(g->dense.mfrag, mfrag.data(), mfrag.size())) ||
-      (rc = upload(g->dense.const_k, const_k, K)) || (rc = upload(g->dense.gfrag, gfrag.data(), gfrag.size())))
+      (rc = g->dense.const_k.reserve(2 * (size_t)K)) || (rc = upload(g->dense.const_k, const_k, K)) || (rc = upload(g->dense.gfrag, gfrag.data(), gfrag.size())))
     return rc;
+  JD_HIP(hipMemset(g->dense.const_k.ptr + K, 0, (size_t)K * sizeof(float)));  // (the residuals of c_k: zero until set)
   if (g->sort.bucket.reserve((size_t)(3 * K + 1)) || hipMemset(g->sort.bucket.ptr, 0, (size_t)(3 * K + 1) * sizeof(int)) != hipSuccess)
     return fail(JD_ERR_ALLOC, "jd_gmm_create: hipMalloc of the bucket counters failed");
   if (!a16.empty()) {
@@ -201,10 +202,29 @@ extern "C" int jd_gmm_set_image_norm(jd_gmm* g, const jd_image_norm* norm) {
   return JD_OK;
 }
 
+// The patch norm the following jd_gmm_prior_* calls of this handle apply (header: jd_gmm_set_patch_norm).
+extern "C" int jd_gmm_set_patch_norm(jd_gmm* g, int kind) {
+  JD_REQUIRE(kind >= 0 && kind < PATCH_NORM_COUNT, "jd_gmm_set_patch_norm: unknown patch norm kind %d", kind);
+  JD_REQUIRE(g, "jd_gmm_set_patch_norm: null argument");
+  g->patch_norm = kind;
+  return JD_OK;
+}
+
+// The part of c_k a float32 const_k cannot hold (header: jd_gmm_set_const_residual): the second half of the constants' array.
+extern "C" int jd_gmm_set_const_residual(jd_gmm* g, const float* residual) {
+  JD_REQUIRE(g && residual, "jd_gmm_set_const_residual: null argument");
+  for (int k = 0; k < g->K; ++k)
+    JD_REQUIRE(std::isfinite(residual[k]), "jd_gmm_set_const_residual: residual[%d] is not finite", k);
+  if (g->d256) return gmm256_set_const_residual(g->d256, residual);
+  JD_HIP(hipDeviceSynchronize());  // (no pass of this handle is reading the constants)
+  JD_HIP(hipMemcpy(g->dense.const_k.ptr + g->K, residual, (size_t)g->K * sizeof(float), hipMemcpyHostToDevice));
+  return JD_OK;
+}
+
 // Backward pass of the arg-max mode without the screen's fused rows: the patches are bucketed by their arg-max component
 // (`arg`), then one wave per 32 patches that share P'_k (gmm_bwd_max_kernel) -> g->dense.gpatch.
 static int bucketed_backward(jd_gmm* g, const float* flux, const PatchGrid& grid, int n_begin, int n_end, const int32_t* arg,
-                             hipStream_t s) {
+                             hipStream_t s, int patch_norm) {
   const long n = n_end - n_begin;
   int rc;
   const size_t slots_cap = (size_t)n + 32 * (size_t)g->K;
@@ -230,7 +250,7 @@ static int bucketed_backward(jd_gmm* g, const float* flux, const PatchGrid& grid
     long bwd_blocks = ((long)(slots_cap / 32) + 3) / 4;
     const long cap = (long)g->n_cu * 3;  // 3 blocks of 4 waves per CU: one wave per SIMD x 3
     if (bwd_blocks > cap) bwd_blocks = cap;
-    launch_bwd_max(b, g->triangular && !opt_is_set(OPT_GMM_DENSE), (unsigned)bwd_blocks, s);
+    launch_bwd_max(b, g->triangular && !opt_is_set(OPT_GMM_DENSE), (unsigned)bwd_blocks, s, patch_norm);
   }
   JD_LAUNCH_CHECK();
   return JD_OK;
@@ -274,6 +294,9 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
   bool screened = false, fused = false, lse_screened = false;
   const ImageNormArgs norm = g->norm;
   const bool has_norm = norm.kind != NORM_IDENTITY;
+  // The standardized patch norm takes the dense kernels only: the screen's error bounds are those of mean-free patches.
+  const int patch_norm = g->patch_norm;
+  const bool screenable = patch_norm == PATCH_NORM_SUBTRACT_MEAN;
   const float* const raw_flux = flux;
   if (phases & 1) {
     if (has_norm) {  // everything below reads n(flux); it still only READS the flux (legal beside the likelihood)
@@ -283,12 +306,12 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
     }
     if ((rc = g->dense.partials.reserve((size_t)((n + 31) / 32 + 4)))) return rc;
     // option JD_GMM_SCREEN = 0 forces the dense fp32 kernel (testing / tuning)
-    screened = !marginalize && g->screen.ok && opt_value(OPT_GMM_SCREEN, 1) != 0 && !opt_is_set(OPT_GMM_DENSE);
+    screened = screenable && !marginalize && g->screen.ok && opt_value(OPT_GMM_SCREEN, 1) != 0 && !opt_is_set(OPT_GMM_DENSE);
     // screened arg-max with a gradient: the exact kernel also produces the gradient rows (no second sort, no separate
     // backward kernel); JD_GMM_FUSED_BWD=0 keeps the bucketed backward pass (testing / tuning)
     fused = screened && grad_flux_accum && g->triangular && opt_value(OPT_GMM_FUSED_BWD, 1) != 0;
     // logsumexp mode with a gradient: through the screen as well (option JD_GMM_LSE_SCREEN = 0: the dense kernels)
-    lse_screened = marginalize && grad_flux_accum && g->screen.ok && g->triangular && g->K <= SCREEN_KC_MAX &&
+    lse_screened = screenable && marginalize && grad_flux_accum && g->screen.ok && g->triangular && g->K <= SCREEN_KC_MAX &&
                         opt_value(OPT_GMM_LSE_SCREEN, 1) != 0 && !opt_is_set(OPT_GMM_DENSE);
     if (lse_screened && g->fused.stats.host && opt_value(OPT_GMM_LSE_SCREEN, 1) != 2) {  // (2: always, for tests and timing)
       volatile int* hs = g->fused.stats.host;
@@ -326,14 +349,14 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
       b.partials = g->dense.partials.ptr;
       n_waves = (int)blocks;
       ProfScope prof(JD_KERNEL_GMM_BWD, s);
-      launch_bwd_lse(b, g->triangular && !opt_is_set(OPT_GMM_DENSE), (unsigned)blocks, s);
+      launch_bwd_lse(b, g->triangular && !opt_is_set(OPT_GMM_DENSE), (unsigned)blocks, s, patch_norm);
       JD_LAUNCH_CHECK();
     } else if (marginalize)
-      rc = launch_fwd(MODE_LSE, a, g->triangular, g->n_cu, s, &n_waves);
+      rc = launch_fwd(MODE_LSE, a, g->triangular, g->n_cu, s, &n_waves, patch_norm);
     else if (screened)
       rc = screened_forward(g, a, s, &n_waves, fused, fused ? g->dense.argmax.ptr : nullptr, (double)value_scale, value_out, accumulate_value);
     else
-      rc = launch_fwd(MODE_MAX, a, g->triangular, g->n_cu, s, &n_waves);
+      rc = launch_fwd(MODE_MAX, a, g->triangular, g->n_cu, s, &n_waves, patch_norm);
     if (rc) return rc;
     // (screened path: the last block of gmm_best_kernel has written the value already)
     if (!screened && !lse_screened &&
@@ -346,17 +369,17 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
     // marginalize: gmm_bwd_lse_kernel has written the rows together with the value; fused: the rows are in g->fused.grec
     // already (after a fallback: in g->dense.gpatch, written by gmm_best_kernel's blocks)
     if (!lse_screened && !marginalize && !fused) {
-      if ((rc = bucketed_backward(g, flux, grid, n_begin, n_end, arg, s))) return rc;
+      if ((rc = bucketed_backward(g, flux, grid, n_begin, n_end, arg, s, patch_norm))) return rc;
     }
 
-    g->pass = GmmPass{true, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, fused, lse_screened, g->screen.gen, shift_dev, norm};
+    g->pass = GmmPass{true, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, fused, lse_screened, g->screen.gen, shift_dev, norm, patch_norm};
     if (!(phases & 2)) return JD_OK;
   } else {
     const GmmPass& ps = g->pass;
     JD_REQUIRE(ps.valid && ps.H == H && ps.W == W && ps.stride == stride && ps.shift_y == shift_y && ps.shift_x == shift_x &&
                    ps.row_begin == patch_row_begin && ps.row_end == patch_row_end && ps.marginalize == marginalize &&
                    ps.gen == g->screen.gen && ps.shift_dev == shift_dev && grad_flux_accum && ps.norm.kind == norm.kind &&
-                   ps.norm.p0 == norm.p0 && ps.norm.p1 == norm.p1,
+                   ps.norm.p0 == norm.p0 && ps.norm.p1 == norm.p1 && ps.patch_norm == patch_norm,
                "jd_gmm_prior_fwd_bwd: phase 2 (gather) without the matching phase 1 of the same pass");
     fused = ps.fused, lse_screened = ps.lse_screened;
   }
@@ -405,7 +428,7 @@ extern "C" int jd_gmm_prior_fwd_bwd(jd_gmm* g, const float* flux, int H, int W, 
       image = g->normed.ptr;
     }
     return gmm256_prior(g->d256, image, flux, norm, H, W, stride, shift_y, shift_x, marginalize, value_scale, value_out,
-                        accumulate_value, grad_coef, grad_flux_accum, argmax_out, shift_dev, s);
+                        accumulate_value, grad_coef, grad_flux_accum, argmax_out, shift_dev, s, g->patch_norm);
   }
   return gmm_prior_impl(g, flux, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, value_scale,
                         value_out, accumulate_value, grad_coef, grad_flux_accum, argmax_out, nullptr, stream, nullptr, shift_dev,

@@ -31,6 +31,9 @@
 // up its column share over all components in 64 NB accumulator registers, the four shares are added in wave order through
 // LDS once per tile, the adjoint of the mean subtraction is applied and one 256-float row per patch is written.
 // Overlap-add: a per-pixel gather over the up to ceil(16 / stride)^2 patches of a pixel in fixed order.
+// Patch norm (template parameter PN): PN_SUBTRACT_MEAN is the x above; PN_STD standardizes, x = (p - mean) / mean
+// (jolideco/utils/norms.py:106-112): a correctly rounded division in load_patches, and in the row epilogue
+// dv/dp_j = (gamma_j - mean(gamma) - (gamma . x) / 256) / mean with x recomputed from the image.
 #include <cmath>
 #include <type_traits>
 #include <vector>
@@ -52,13 +55,14 @@ constexpr int TILE_MAX = 32;             // patches per block: 16 NB, NB = 1 | 2
 constexpr int GPITCH = 260;              // floats per patch row of the block's gradient sum in LDS (16-byte aligned rows)
 
 enum { M_MAX = 0, M_LSE = 1, M_DENSE = 2 };
+enum { PN_SUBTRACT_MEAN = 0, PN_STD = 1 };  // jd_gmm_set_patch_norm
 
 struct Args256 {
   const float* image;    // (H, W) | M_DENSE: (n, 256) explicit patches
   const float* afrag;    // K * FRAG_FLOATS
   const float* gfrag;    // K * FRAG_FLOATS
   const float* mfrag;    // K * 256: -m'[j]
-  const float* const_k;  // K
+  const float* const_k;  // K constants c_k, then K residuals (gmm256_set_const_residual; read under PN_STD only)
   int K, H, W, stride, nPx, shift_y, shift_x;
   const int* shift_dev;  // nullable, device [2] = {shift_y, shift_x} residues: read instead of the two members above
   int n_end;             // number of patches
@@ -113,10 +117,10 @@ __device__ __forceinline__ void load_chunk(float4 (&buf)[4], const float4* frag,
 // The tile's patches in B-operand order: x[nb][s] = pixel 4 s + g of patch tile_base + 16 nb + n16, mean subtracted;
 // ok[nb]: the patch exists and passes the reference's `> -1e5` filter (all zeros otherwise).  The mean is summed in ONE
 // order (64 pixels in lane order, then the four lane groups) by the forward and the backward kernel, which therefore see
-// the same bits.
-template <bool DENSE, int NB>
+// the same bits.  mean_out[nb]: that mean (the row epilogue of the standardized norm divides by it).
+template <bool DENSE, int NB, int PN = PN_SUBTRACT_MEAN>
 __device__ __forceinline__ void load_patches(float (&x)[NB][64], bool (&ok)[NB], const Args256& a, int tile_base, int g,
-                                             int n16) {
+                                             int n16, float* mean_out = nullptr) {
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int n = tile_base + 16 * nb + n16;
@@ -148,8 +152,14 @@ __device__ __forceinline__ void load_patches(float (&x)[NB][64], bool (&ok)[NB],
     seli &= __shfl_xor(seli, 16, 64);
     seli &= __shfl_xor(seli, 32, 64);
     ok[nb] = valid && seli != 0;
+    if constexpr (PN == PN_STD) {
+      if (mean_out) mean_out[nb] = mean;
 #pragma unroll
-    for (int s = 0; s < 64; ++s) x[nb][s] = ok[nb] ? x[nb][s] - mean : 0.f;
+      for (int s = 0; s < 64; ++s) x[nb][s] = ok[nb] ? (x[nb][s] - mean) / mean : 0.f;
+    } else {
+#pragma unroll
+      for (int s = 0; s < 64; ++s) x[nb][s] = ok[nb] ? x[nb][s] - mean : 0.f;
+    }
   }
 }
 
@@ -225,7 +235,7 @@ __device__ __forceinline__ void exchange_q(float (&l)[NB], const f32x4 (&y)[4][N
   }
 }
 
-template <int MODE, bool TRI, int NB>
+template <int MODE, bool TRI, int NB, int PN = PN_SUBTRACT_MEAN>
 __global__ __launch_bounds__(256, 1) void gmm256_fwd_kernel(Args256 a) {
   if (a.shift_dev) a.shift_y = a.shift_dev[0], a.shift_x = a.shift_dev[1];
   __shared__ float qbuf[2][4][TILE_MAX];
@@ -234,7 +244,7 @@ __global__ __launch_bounds__(256, 1) void gmm256_fwd_kernel(Args256 a) {
 
   float x[NB][64];
   bool ok[NB];
-  load_patches<MODE == M_DENSE, NB>(x, ok, a, tile_base, g, n16);
+  load_patches<MODE == M_DENSE, NB, PN>(x, ok, a, tile_base, g, n16);
 
   float best[NB], aux[NB];  // aux: arg-max (as int bits) | sum-exp
 #pragma unroll
@@ -246,6 +256,10 @@ __global__ __launch_bounds__(256, 1) void gmm256_fwd_kernel(Args256 a) {
     whiten<TRI, NB>(y, x, abuf, a, k, k + 1 < a.K ? k + 1 : k, lane, wave);
     float l[NB];
     exchange_q<NB>(l, y, qbuf, k & 1, a.const_k[k], lane, wave);
+    if constexpr (PN == PN_STD) {  // the residual of c_k (jd_gmm_set_const_residual): l is a small difference under this norm
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) l[nb] += a.const_k[a.K + k];
+    }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       if (MODE == M_MAX) {
@@ -280,7 +294,7 @@ __global__ __launch_bounds__(256, 1) void gmm256_fwd_kernel(Args256 a) {
   if (lane == 0) a.partials[blockIdx.x] = local;
 }
 
-template <int MODE, bool TRI, int NB>
+template <int MODE, bool TRI, int NB, int PN = PN_SUBTRACT_MEAN>
 __global__ __launch_bounds__(256, 1) void gmm256_bwd_kernel(Args256 a) {
   constexpr int TILE = 16 * NB;
   if (a.shift_dev) a.shift_y = a.shift_dev[0], a.shift_x = a.shift_dev[1];
@@ -293,7 +307,17 @@ __global__ __launch_bounds__(256, 1) void gmm256_bwd_kernel(Args256 a) {
 
   float x[NB][64];
   bool ok[NB];
-  load_patches<false, NB>(x, ok, a, tile_base, g, n16);
+  __shared__ float pmean_s[PN == PN_STD ? TILE : 1];  // PN_STD: mean of every patch of the tile, NaN for a filtered one
+  if constexpr (PN == PN_STD) {
+    float pmean[NB];
+    load_patches<false, NB, PN>(x, ok, a, tile_base, g, n16, pmean);
+    if (wave == 0 && g == 0) {
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) pmean_s[16 * nb + n16] = ok[nb] ? pmean[nb] : NAN;  // (read behind the barriers below)
+    }
+  } else {
+    load_patches<false, NB>(x, ok, a, tile_base, g, n16);
+  }
 
   int win[NB];
   float lse[NB];
@@ -356,6 +380,10 @@ __global__ __launch_bounds__(256, 1) void gmm256_bwd_kernel(Args256 a) {
     } else {
       float l[NB];
       exchange_q<NB>(l, y, qbuf, idx & 1, a.const_k[k], lane, wave);
+      if constexpr (PN == PN_STD) {  // (the forward kernel's l)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) l[nb] += a.const_k[a.K + k];
+      }
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) r[nb] = ok[nb] ? expf(l[nb] - lse[nb]) : 0.f;
     }
@@ -403,7 +431,24 @@ __global__ __launch_bounds__(256, 1) void gmm256_bwd_kernel(Args256 a) {
     const int n = tile_base + p;
     const float4 v = *reinterpret_cast<const float4*>(gs + p * GPITCH + 4 * lane);
     const float mean = wave_sum((v.x + v.y) + (v.z + v.w)) * (1.f / 256.f);
-    if (n < a.n_end)
+    if constexpr (PN == PN_STD) {
+      // lane holds gamma of pixels 4 lane .. 4 lane + 3: row lane / 4, columns 4 (lane % 4) ..
+      if (n >= a.n_end) continue;  // (wave-uniform)
+      const float m = pmean_s[p];
+      float4 out = make_float4(0.f, 0.f, 0.f, 0.f);  // a filtered patch: an exact zero row
+      if (m == m) {
+        const int py = n / a.nPx, px = n % a.nPx;
+        const float* row = a.image + (size_t)wrap(py * a.stride + (lane >> 2) - a.shift_y, a.H) * a.W;
+        const float vv[4] = {v.x, v.y, v.z, v.w};
+        float dot = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          dot = fmaf(vv[j], (row[wrap(px * a.stride + 4 * (lane & 3) + j - a.shift_x, a.W)] - m) / m, dot);
+        const float c = mean + wave_sum(dot) * (1.f / 256.f);
+        out = make_float4((v.x - c) / m, (v.y - c) / m, (v.z - c) / m, (v.w - c) / m);
+      }
+      *reinterpret_cast<float4*>(a.gpatch + (size_t)n * D256 + 4 * lane) = out;
+    } else if (n < a.n_end)
       *reinterpret_cast<float4*>(a.gpatch + (size_t)n * D256 + 4 * lane) =
           make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
   }
@@ -485,6 +530,12 @@ void gmm256_destroy(Gmm256* g) {
 
 bool gmm256_is_triangular(const Gmm256* g) { return g->triangular; }
 
+int gmm256_set_const_residual(Gmm256* g, const float* residual) {
+  JD_HIP(hipDeviceSynchronize());  // (no pass of this handle is reading the constants)
+  JD_HIP(hipMemcpy(g->const_k + g->K, residual, (size_t)g->K * sizeof(float), hipMemcpyHostToDevice));
+  return JD_OK;
+}
+
 int gmm256_create(int K, const float* prec_chol, const float* mu_prec, const float* const_k, const float* pixel_w,
                   Gmm256** out) {
   Gmm256* g = new (std::nothrow) Gmm256();
@@ -492,7 +543,7 @@ int gmm256_create(int K, const float* prec_chol, const float* mu_prec, const flo
   g->K = K;
   const size_t kf = (size_t)K * FRAG_FLOATS;
   auto alloc = [&](float** dst, size_t n) { return hipMalloc(dst, n * sizeof(float)) == hipSuccess; };
-  if (!alloc(&g->afrag, kf) || !alloc(&g->gfrag, kf) || !alloc(&g->mfrag, (size_t)K * D256) || !alloc(&g->const_k, K)) {
+  if (!alloc(&g->afrag, kf) || !alloc(&g->gfrag, kf) || !alloc(&g->mfrag, (size_t)K * D256) || !alloc(&g->const_k, 2 * (size_t)K)) {
     gmm256_destroy(g);
     return fail(JD_ERR_ALLOC, "jd_gmm_create: hipMalloc of the D = 256 fragments (%zu MB) failed", 2 * kf * sizeof(float) >> 20);
   }
@@ -532,7 +583,8 @@ int gmm256_create(int K, const float* prec_chol, const float* mu_prec, const flo
       return fail(JD_ERR_HIP, "jd_gmm_create: upload of the D = 256 fragments failed");
     }
   }
-  if (hipMemcpy(g->const_k, const_k, (size_t)K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpy(g->const_k, const_k, (size_t)K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(g->const_k + K, 0, (size_t)K * sizeof(float)) != hipSuccess) {  // (the residuals: zero until set)
     gmm256_destroy(g);
     return fail(JD_ERR_HIP, "jd_gmm_create: upload of the D = 256 constants failed");
   }
@@ -558,23 +610,25 @@ static Args256 base_args(const Gmm256* g) {
 // backward instantiation needs more registers than a wave has and would spill.
 static int tile_halves(long n, int n_cu, bool tri) { return tri && (n + TILE_MAX - 1) / TILE_MAX >= n_cu ? 2 : 1; }
 
-template <int MODE>
+template <int MODE, int PN = PN_SUBTRACT_MEAN>
 static void launch_fwd256(const Args256& a, bool tri, int nb, unsigned tiles, hipStream_t s) {
-  if (!tri) gmm256_fwd_kernel<MODE, false, 1><<<tiles, 256, 0, s>>>(a);
-  else if (nb == 2) gmm256_fwd_kernel<MODE, true, 2><<<tiles, 256, 0, s>>>(a);
-  else gmm256_fwd_kernel<MODE, true, 1><<<tiles, 256, 0, s>>>(a);
+  if (!tri) gmm256_fwd_kernel<MODE, false, 1, PN><<<tiles, 256, 0, s>>>(a);
+  else if (nb == 2) gmm256_fwd_kernel<MODE, true, 2, PN><<<tiles, 256, 0, s>>>(a);
+  else gmm256_fwd_kernel<MODE, true, 1, PN><<<tiles, 256, 0, s>>>(a);
 }
 
-template <int MODE>
+template <int MODE, int PN = PN_SUBTRACT_MEAN>
 static void launch_bwd256(const Args256& a, bool tri, int nb, unsigned tiles, hipStream_t s) {
-  if (!tri) gmm256_bwd_kernel<MODE, false, 1><<<tiles, 256, 0, s>>>(a);
-  else if (nb == 2) gmm256_bwd_kernel<MODE, true, 2><<<tiles, 256, 0, s>>>(a);
-  else gmm256_bwd_kernel<MODE, true, 1><<<tiles, 256, 0, s>>>(a);
+  if (!tri) gmm256_bwd_kernel<MODE, false, 1, PN><<<tiles, 256, 0, s>>>(a);
+  else if (nb == 2) gmm256_bwd_kernel<MODE, true, 2, PN><<<tiles, 256, 0, s>>>(a);
+  else gmm256_bwd_kernel<MODE, true, 1, PN><<<tiles, 256, 0, s>>>(a);
 }
 
 int gmm256_prior(Gmm256* g, const float* image, const float* raw_flux, const ImageNormArgs& norm, int H, int W, int stride,
                  int shift_y, int shift_x, int marginalize, float value_scale, float* value_out, int accumulate_value,
-                 float grad_coef, float* grad_flux_accum, int32_t* argmax_out, const int* shift_dev, hipStream_t s) {
+                 float grad_coef, float* grad_flux_accum, int32_t* argmax_out, const int* shift_dev, hipStream_t s,
+                 int patch_norm) {
+  const bool std_norm = patch_norm == PN_STD;
   JD_REQUIRE(H >= P16 && W >= P16, "jd_gmm_prior_fwd_bwd: image (%d, %d) smaller than a 16x16 patch (D = 256)", H, W);
   JD_REQUIRE(stride >= 1 && stride <= P16, "jd_gmm_prior_fwd_bwd: stride = %d not in [1, 16] (D = 256)", stride);
   const int nPy = (H - P16) / stride + 1, nPx = (W - P16) / stride + 1;
@@ -601,7 +655,9 @@ int gmm256_prior(Gmm256* g, const float* image, const float* raw_flux, const Ima
   }
   {
     ProfScope prof(JD_KERNEL_GMM_FWD, s);
-    if (marginalize) launch_fwd256<M_LSE>(a, g->triangular, nb, tiles, s);
+    if (marginalize && std_norm) launch_fwd256<M_LSE, PN_STD>(a, g->triangular, nb, tiles, s);
+    else if (marginalize) launch_fwd256<M_LSE>(a, g->triangular, nb, tiles, s);
+    else if (std_norm) launch_fwd256<M_MAX, PN_STD>(a, g->triangular, nb, tiles, s);
     else launch_fwd256<M_MAX>(a, g->triangular, nb, tiles, s);
     JD_LAUNCH_CHECK();
     if ((rc = launch_finalize_sum(g->partials, (int)tiles, (double)value_scale, 0.0, value_out, accumulate_value, s))) return rc;
@@ -612,7 +668,9 @@ int gmm256_prior(Gmm256* g, const float* image, const float* raw_flux, const Ima
   a.gpatch = g->gpatch;
   {
     ProfScope prof(JD_KERNEL_GMM_BWD, s);
-    if (marginalize) launch_bwd256<M_LSE>(a, g->triangular, nb, tiles, s);
+    if (marginalize && std_norm) launch_bwd256<M_LSE, PN_STD>(a, g->triangular, nb, tiles, s);
+    else if (marginalize) launch_bwd256<M_LSE>(a, g->triangular, nb, tiles, s);
+    else if (std_norm) launch_bwd256<M_MAX, PN_STD>(a, g->triangular, nb, tiles, s);
     else launch_bwd256<M_MAX>(a, g->triangular, nb, tiles, s);
     JD_LAUNCH_CHECK();
   }

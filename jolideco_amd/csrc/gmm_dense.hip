@@ -22,11 +22,14 @@
 // Backward (max mode): the patches are bucketed by arg-max component; one wave takes 32 patches that
 // share P'_k and runs y = x^T P' - m' and gamma = -P' y on the matrix cores (same block skipping);
 // the overlap-add is done race-free and in a fixed order by a gather pass.
+// Patch norm (template parameter PN of the kernels that cut patches out of the image): PATCH_NORM_SUBTRACT_MEAN is the
+// x above; PATCH_NORM_STD standardizes, x = (p - mean) / mean (jolideco/utils/norms.py:106-112) -- a correctly rounded
+// division in the staging and standardized_row_offset in the row epilogues; everything between is the same code.
 #include "gmm_internal.h"
 
 namespace jd {
 
-template <int TB, int MODE, bool TRI>
+template <int TB, int MODE, bool TRI, int PN = PATCH_NORM_SUBTRACT_MEAN>
 __global__ __launch_bounds__(256, 1) void gmm_fwd_kernel(GmmFwdArgs a) {
   use_device_shift(a);
   if (a.run_flag && *a.run_flag != a.run_gen) return;
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(256, 1) void gmm_fwd_kernel(GmmFwdArgs a) {
         }
         const float mean = patch_mean_halves(x);  // SubtractMeanPatchNorm, utils/norms.py:100-103
 #pragma unroll
-        for (int s = 0; s < 32; ++s) x[s] -= mean;
+        for (int s = 0; s < 32; ++s) x[s] = PN == PATCH_NORM_STD ? (x[s] - mean) / mean : x[s] - mean;
         // NOT `sel && shfl(...)`: the short circuit would keep the lanes with sel == false out of the exchange and the
         // other half of the patch would read a stale register
         const int sel_other = __shfl_xor((int)sel, 32, 64);
@@ -97,9 +100,9 @@ __global__ __launch_bounds__(256, 1) void gmm_fwd_kernel(GmmFwdArgs a) {
     for (int k = k0; k < k1; k += 2) {
       // prefetch is unconditional (clamped): a branch would force a full vmcnt(0) drain
       load_frags<TRI>(f1, af, mf, k + 1 < k1 ? k + 1 : k);
-      sweep_tiles<TB, MODE, TRI>(f0, xs_lane, st_lane, a.const_k[k], k, a, n_lane, g == 0);
+      sweep_tiles<TB, MODE, TRI, PN>(f0, xs_lane, st_lane, a.const_k[k], k, a, n_lane, g == 0);
       load_frags<TRI>(f0, af, mf, k + 2 < k1 ? k + 2 : k);
-      if (k + 1 < k1) sweep_tiles<TB, MODE, TRI>(f1, xs_lane, st_lane, a.const_k[k + 1], k + 1, a, n_lane, g == 0);
+      if (k + 1 < k1) sweep_tiles<TB, MODE, TRI, PN>(f1, xs_lane, st_lane, a.const_k[k + 1], k + 1, a, n_lane, g == 0);
     }
   }
   if (MODE == MODE_DENSE) return;
@@ -153,7 +156,7 @@ __global__ __launch_bounds__(256, 1) void gmm_fwd_kernel(GmmFwdArgs a) {
 //                                this product are laid out on the host in exactly that order, so no
 //                                lane movement / LDS is needed; blocks jb < ib are zero and skipped)
 // ------------------------------------------------------------------------------------------
-template <bool TRI>
+template <bool TRI, int PN = PATCH_NORM_SUBTRACT_MEAN>
 __global__ __launch_bounds__(256) void gmm_bwd_max_kernel(GmmBwdArgs a) {
   use_device_shift(a);
   const int lane = threadIdx.x & 63;
@@ -169,6 +172,7 @@ __global__ __launch_bounds__(256) void gmm_bwd_max_kernel(GmmBwdArgs a) {
     bool valid[2];
     // ---- B operand: x[nb][st] = pixel 4 st + g of patch 16 nb + n16, mean subtracted ------------
     float x[2][16];
+    StdPatch sp[2];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
       const int slot = 32 * grp + 16 * nb + n16;
@@ -184,13 +188,17 @@ __global__ __launch_bounds__(256) void gmm_bwd_max_kernel(GmmBwdArgs a) {
       }
       const float mean = patch_mean_groups(x[nb]);
 #pragma unroll
-      for (int st = 0; st < 16; ++st) x[nb][st] -= mean;
+      for (int st = 0; st < 16; ++st) x[nb][st] = PN == PATCH_NORM_STD ? (x[nb][st] - mean) / mean : x[nb][st] - mean;
+      sp[nb] = StdPatch{py, px, mean};
     }
 
     f32x4 y[4][2];
     whiten_columns<TRI>(y, x, a.afrag, a.mfrag, k, lane);
     float* rows[2] = {a.gpatch + (size_t)(valid[0] ? n[0] - a.n_begin : 0) * D, a.gpatch + (size_t)(valid[1] ? n[1] - a.n_begin : 0) * D};
-    patch_gradient_rows<TRI>(y, a.gfrag, k, lane, valid, rows);
+    if constexpr (PN == PATCH_NORM_STD)
+      patch_gradient_rows<TRI, PN>(y, a.gfrag, k, lane, valid, rows, &a, sp);
+    else
+      patch_gradient_rows<TRI>(y, a.gfrag, k, lane, valid, rows);
   }
 }
 
@@ -220,16 +228,18 @@ __device__ __forceinline__ void load_gfrags(GFrag& f, const float4* gf, int k) {
 // S and the gradient accumulator G are rescaled by exp(m_old - m_new) -- a wave-uniform branch, taken only while some
 // patch of the wave still sees its maximum rise -- and the component enters with the weight e = exp(l - m):
 // S += e, G += P' (e y).  At the end v = m + log S and the gradient row is G / S.
-template <bool TRI, int GRP>
+// PN = PATCH_NORM_STD: l takes the residual ck_lo of c_k as well (finish_tile: the same l as the forward kernel's).
+template <bool TRI, int GRP, int PN = PATCH_NORM_SUBTRACT_MEAN>
 __device__ __forceinline__ void lse_component(const FragBuf& f, const GFrag& gfr, float ck, const float4 (&x)[GRP][8],
-                                              float (&m)[GRP][2], float (&S)[GRP][2], f32x4 (&G)[GRP][4][2]) {
+                                              float (&m)[GRP][2], float (&S)[GRP][2], f32x4 (&G)[GRP][4][2], float ck_lo = 0.f) {
 #pragma unroll
   for (int gi = 0; gi < GRP; ++gi) {
     f32x4 y[4][2];
     mfma_tile<TRI>(y, f, x[gi]);
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
-      const float l = fmaf(-0.5f, sum_lane_groups(sum_squares(y, nb)), ck);
+      float l = fmaf(-0.5f, sum_lane_groups(sum_squares(y, nb)), ck);
+      if constexpr (PN == PATCH_NORM_STD) l += ck_lo;
       const bool rises = l > m[gi][nb];
       if (__ballot(rises) != 0ull) {
         const float m_new = rises ? l : m[gi][nb];
@@ -265,7 +275,7 @@ __device__ __forceinline__ void lse_component(const FragBuf& f, const GFrag& gfr
 // per block, gamma = -sum_k r_k P'_k y_k minus its mean -> gpatch.  (Until late in round 3 a forward kernel computed v
 // first and this kernel evaluated every l_k a second time to form r_k = exp(l_k - v): three matrix products per
 // component instead of two.)
-template <bool TRI, int GRP>
+template <bool TRI, int GRP, int PN = PATCH_NORM_SUBTRACT_MEAN>
 __global__ __launch_bounds__(256, 1) void gmm_bwd_lse_kernel(GmmBwdLseArgs a) {
   use_device_shift(a);
   const bool everything = !a.mark || *a.run_flag == a.run_gen;
@@ -285,6 +295,7 @@ __global__ __launch_bounds__(256, 1) void gmm_bwd_lse_kernel(GmmBwdLseArgs a) {
     int n[GRP][2];
     bool valid[GRP][2], sel[GRP][2], mine[GRP][2];
     float m[GRP][2], S[GRP][2];
+    float pmean[GRP][2];  // (PATCH_NORM_STD: the patch means, for the row epilogue)
     float4 x[GRP][8];
     f32x4 G[GRP][4][2];
 #pragma unroll
@@ -321,10 +332,16 @@ __global__ __launch_bounds__(256, 1) void gmm_bwd_lse_kernel(GmmBwdLseArgs a) {
         keep &= __shfl_xor(keep, 32, 64);
         sel[gi][nb] = valid[gi][nb] && keep != 0;
         const float mean = patch_mean_groups(xv);
+        pmean[gi][nb] = mean;
+        if (PN == PATCH_NORM_STD) {
 #pragma unroll
-        for (int st4 = 0; st4 < 4; ++st4)
-          x[gi][nb * 4 + st4] = make_float4(xv[4 * st4] - mean, xv[4 * st4 + 1] - mean, xv[4 * st4 + 2] - mean,
-                                            xv[4 * st4 + 3] - mean);
+          for (int st = 0; st < 16; ++st) xv[st] = (xv[st] - mean) / mean;
+        } else {
+#pragma unroll
+          for (int st = 0; st < 16; ++st) xv[st] -= mean;
+        }
+#pragma unroll
+        for (int st4 = 0; st4 < 4; ++st4) x[gi][nb * 4 + st4] = make_float4(xv[4 * st4], xv[4 * st4 + 1], xv[4 * st4 + 2], xv[4 * st4 + 3]);
 #pragma unroll
         for (int ib = 0; ib < 4; ++ib) G[gi][ib][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -337,11 +354,18 @@ __global__ __launch_bounds__(256, 1) void gmm_bwd_lse_kernel(GmmBwdLseArgs a) {
       const int kn = k + 1 < a.K ? k + 1 : k;
       load_frags<TRI>(f1, af, mf, kn);
       load_gfrags<TRI>(g1, gf, kn);
-      lse_component<TRI, GRP>(f0, g0, a.const_k[k], x, m, S, G);
+      if constexpr (PN == PATCH_NORM_STD)
+        lse_component<TRI, GRP, PN>(f0, g0, a.const_k[k], x, m, S, G, a.const_k[a.K + k]);
+      else
+        lse_component<TRI, GRP>(f0, g0, a.const_k[k], x, m, S, G);
       const int kn2 = k + 2 < a.K ? k + 2 : k;
       load_frags<TRI>(f0, af, mf, kn2);
       load_gfrags<TRI>(g0, gf, kn2);
-      if (k + 1 < a.K) lse_component<TRI, GRP>(f1, g1, a.const_k[k + 1], x, m, S, G);
+      if constexpr (PN == PATCH_NORM_STD) {
+        if (k + 1 < a.K) lse_component<TRI, GRP, PN>(f1, g1, a.const_k[k + 1], x, m, S, G, a.const_k[a.K + k + 1]);
+      } else {
+        if (k + 1 < a.K) lse_component<TRI, GRP>(f1, g1, a.const_k[k + 1], x, m, S, G);
+      }
     }
 
     // v = m + log S; gamma = -G / S, minus its mean over the 64 pixels (adjoint of the patch-mean subtraction); a
@@ -358,12 +382,27 @@ __global__ __launch_bounds__(256, 1) void gmm_bwd_lse_kernel(GmmBwdLseArgs a) {
           sum += (G[gi][ib][nb][0] + G[gi][ib][nb][1]) + (G[gi][ib][nb][2] + G[gi][ib][nb][3]);
         }
         const float mean = sum_lane_groups(sum) * (1.f / 64.f);
+        float c = mean, inv_m = 1.f;  // PATCH_NORM_STD: the row is (c - G) / m (a filtered patch: an exact zero row)
+        if constexpr (PN == PATCH_NORM_STD) {
+          const float pm = pmean[gi][nb];
+          const int py = valid[gi][nb] ? n[gi][nb] / a.nPx : 0, px = valid[gi][nb] ? n[gi][nb] % a.nPx : 0;
+          c = standardized_row_offset(a, py, px, g, pm, mean, [&](int ib, int e) { return G[gi][ib][nb][e]; });
+          inv_m = 1.f / pm;
+        }
         if (mine[gi][nb]) {
           float4* out = reinterpret_cast<float4*>(a.gpatch + (size_t)(n[gi][nb] - a.n_begin) * D);
+          if constexpr (PN == PATCH_NORM_STD) {
 #pragma unroll
-          for (int ib = 0; ib < 4; ++ib)
-            out[4 * ib + g] = make_float4(mean - G[gi][ib][nb][0], mean - G[gi][ib][nb][1], mean - G[gi][ib][nb][2],
-                                          mean - G[gi][ib][nb][3]);
+            for (int ib = 0; ib < 4; ++ib)
+              out[4 * ib + g] = sel[gi][nb] ? make_float4((c - G[gi][ib][nb][0]) * inv_m, (c - G[gi][ib][nb][1]) * inv_m,
+                                                          (c - G[gi][ib][nb][2]) * inv_m, (c - G[gi][ib][nb][3]) * inv_m)
+                                            : make_float4(0.f, 0.f, 0.f, 0.f);
+          } else {
+#pragma unroll
+            for (int ib = 0; ib < 4; ++ib)
+              out[4 * ib + g] = make_float4(mean - G[gi][ib][nb][0], mean - G[gi][ib][nb][1], mean - G[gi][ib][nb][2],
+                                            mean - G[gi][ib][nb][3]);
+          }
           const float v = sel[gi][nb] ? m[gi][nb] + logf(S[gi][nb]) : 0.f;
           if (g == 0 && a.vpatch) a.vpatch[n[gi][nb]] = v;
           if (g == 0 && sel[gi][nb]) local += (double)v;
@@ -395,39 +434,42 @@ static int pick_block_tiles(long n_patches, int n_cu) {
   return best_tb;
 }
 
-template <int TB, int MODE, bool TRI>
+template <int TB, int MODE, bool TRI, int PN>
 static int launch_fwd_tb(const GmmFwdArgs& a, unsigned blocks, hipStream_t s) {
   const size_t lds = (size_t)(TB * 2048 + 4 * TB * 64 + TB * 32) * sizeof(float);
   static bool configured = false;
   if (!configured) {
-    JD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gmm_fwd_kernel<TB, MODE, TRI>),
+    JD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gmm_fwd_kernel<TB, MODE, TRI, PN>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     configured = true;
   }
-  gmm_fwd_kernel<TB, MODE, TRI><<<blocks, 256, lds, s>>>(a);
+  gmm_fwd_kernel<TB, MODE, TRI, PN><<<blocks, 256, lds, s>>>(a);
   JD_LAUNCH_CHECK();
   return JD_OK;
 }
 
 // tiles per block -> instantiation
-template <int MODE, bool TRI>
+template <int MODE, bool TRI, int PN>
 static int launch_fwd_tiles(int tb, const GmmFwdArgs& a, unsigned blocks, hipStream_t s) {
   switch (tb) {
-    case 16: return launch_fwd_tb<16, MODE, TRI>(a, blocks, s);
-    case 8: return launch_fwd_tb<8, MODE, TRI>(a, blocks, s);
-    default: return launch_fwd_tb<4, MODE, TRI>(a, blocks, s);
+    case 16: return launch_fwd_tb<16, MODE, TRI, PN>(a, blocks, s);
+    case 8: return launch_fwd_tb<8, MODE, TRI, PN>(a, blocks, s);
+    default: return launch_fwd_tb<4, MODE, TRI, PN>(a, blocks, s);
   }
 }
-template <int MODE>
+template <int MODE, int PN = PATCH_NORM_SUBTRACT_MEAN>
 static int launch_fwd_mode(bool tri, int tb, const GmmFwdArgs& a, unsigned blocks, hipStream_t s) {
-  return tri ? launch_fwd_tiles<MODE, true>(tb, a, blocks, s) : launch_fwd_tiles<MODE, false>(tb, a, blocks, s);
+  return tri ? launch_fwd_tiles<MODE, true, PN>(tb, a, blocks, s) : launch_fwd_tiles<MODE, false, PN>(tb, a, blocks, s);
 }
 
-int launch_fwd_blocks(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStream_t s, int* n_partials) {
+int launch_fwd_blocks(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStream_t s, int* n_partials, int patch_norm) {
   const long n = a.n_end - a.n_begin;
   const int tb = pick_block_tiles(n, n_cu);
   const unsigned blocks = (unsigned)((n + 32L * tb - 1) / (32L * tb));
   *n_partials = (int)blocks;
+  if (patch_norm == PATCH_NORM_STD && mode != MODE_DENSE)
+    return mode == MODE_MAX ? launch_fwd_mode<MODE_MAX, PATCH_NORM_STD>(tri, tb, a, blocks, s)
+                            : launch_fwd_mode<MODE_LSE, PATCH_NORM_STD>(tri, tb, a, blocks, s);
   switch (mode) {
     case MODE_MAX: return launch_fwd_mode<MODE_MAX>(tri, tb, a, blocks, s);
     case MODE_LSE: return launch_fwd_mode<MODE_LSE>(tri, tb, a, blocks, s);
@@ -435,21 +477,33 @@ int launch_fwd_blocks(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStre
   }
 }
 
-int launch_fwd(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStream_t s, int* n_partials) {
+int launch_fwd(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStream_t s, int* n_partials, int patch_norm) {
   if (opt_is_set(OPT_GMM_DENSE)) tri = false;  // tuning / testing: force the dense variant
   ProfScope prof(JD_KERNEL_GMM_FWD, s);
-  return launch_fwd_blocks(mode, a, tri, n_cu, s, n_partials);
+  return launch_fwd_blocks(mode, a, tri, n_cu, s, n_partials, patch_norm);
 }
 
-void launch_bwd_max(const GmmBwdArgs& b, bool tri, unsigned blocks, hipStream_t s) {
-  if (tri)
+void launch_bwd_max(const GmmBwdArgs& b, bool tri, unsigned blocks, hipStream_t s, int patch_norm) {
+  if (patch_norm == PATCH_NORM_STD) {
+    if (tri)
+      gmm_bwd_max_kernel<true, PATCH_NORM_STD><<<blocks, 256, 0, s>>>(b);
+    else
+      gmm_bwd_max_kernel<false, PATCH_NORM_STD><<<blocks, 256, 0, s>>>(b);
+  } else if (tri)
     gmm_bwd_max_kernel<true><<<blocks, 256, 0, s>>>(b);
   else
     gmm_bwd_max_kernel<false><<<blocks, 256, 0, s>>>(b);
 }
 
-void launch_bwd_lse(const GmmBwdLseArgs& b, bool tri, unsigned blocks, hipStream_t s) {
-  if (tri)
+void launch_bwd_lse(const GmmBwdLseArgs& b, bool tri, unsigned blocks, hipStream_t s, int patch_norm) {
+  if (patch_norm == PATCH_NORM_STD) {
+    if (tri)
+      gmm_bwd_lse_kernel<true, 2, PATCH_NORM_STD><<<blocks, 256, 0, s>>>(b);
+    else
+      // one group per wave: with two, the factors that skip nothing and the means of this norm do not fit the registers
+      // (the kernel strides over the groups whatever the grid was sized for)
+      gmm_bwd_lse_kernel<false, 1, PATCH_NORM_STD><<<blocks, 256, 0, s>>>(b);
+  } else if (tri)
     gmm_bwd_lse_kernel<true, 2><<<blocks, 256, 0, s>>>(b);
   else
     gmm_bwd_lse_kernel<false, 2><<<blocks, 256, 0, s>>>(b);

@@ -24,6 +24,9 @@ constexpr int D = 64;  // features per patch
 constexpr int AFRAG_FLOATS = 4 * 4 * 64 * 4;
 
 enum { MODE_MAX = 0, MODE_LSE = 1, MODE_DENSE = 2 };
+// patch norm of a pass (jd_gmm_set_patch_norm): x = p - mean(p) | x = (p - mean(p)) / mean(p); a compile-time parameter
+// of the dense kernels, which fuse it
+enum { PATCH_NORM_SUBTRACT_MEAN = 0, PATCH_NORM_STD = 1, PATCH_NORM_COUNT = 2 };
 
 __host__ __device__ inline unsigned long long best_key(float l, int k) {
   unsigned u = 0;
@@ -46,7 +49,7 @@ struct GmmFwdArgs {
   const float* flux;     // (H, W) image  | MODE_DENSE: (n, 64) explicit patches
   const float* afrag;    // K * AFRAG_FLOATS
   const float* mfrag;    // K * 64: [jb 4][g 4][r 4] = -m'[16 jb + 4 g + r]
-  const float* const_k;  // K
+  const float* const_k;  // K constants c_k, then K residuals (jd_gmm_set_const_residual; read under PATCH_NORM_STD only)
   int K, H, W, stride, nPx, shift_y, shift_x;
   const int* shift_dev;  // nullable, device [2] = {shift_y, shift_x} residues: read instead of the two members above (use_device_shift)
   int n_begin, n_end;    // linear patch index range (row-major over the patch grid)
@@ -109,6 +112,27 @@ __device__ __forceinline__ float patch_mean_halves(const float (&x)[32]) {
     t[g] = sg + __shfl_xor(sg, 32, 64);
   }
   return ((t[0] + t[1]) + (t[2] + t[3])) * (1.f / 64.f);
+}
+
+// Backward of the standardized patch norm x = (p - m) / m, m = mean(p): with gamma = dv/dx the row is
+//   dv/dp_j = (gamma_j - mean(gamma) - (gamma . x) / 64) / m .
+// The row epilogues hold G = -gamma with pixel 16 ib + 4 g + e in register e of block ib (G(ib, e)); x is recomputed
+// there from the image and the mean m of the staging (the same bits), so the component loops carry nothing for it.
+// Returns mean(G) + (G . x) / 64 given mean(G): the row is (that - G_j) / m.
+template <class A, class F>
+__device__ __forceinline__ float standardized_row_offset(const A& a, int py, int px, int g, float m, float mean_g, F&& G) {
+  float dot = 0.f;
+#pragma unroll
+  for (int ib = 0; ib < 4; ++ib) {
+    const int yy = wrap(py * a.stride + 2 * ib + (g >> 1) - a.shift_y, a.H);
+    const float* row = a.flux + (size_t)yy * a.W;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int xx = wrap(px * a.stride + 4 * (g & 1) + e - a.shift_x, a.W);
+      dot = fmaf(G(ib, e), (row[xx] - m) / m, dot);
+    }
+  }
+  return mean_g + sum_lane_groups(dot) * (1.f / 64.f);
 }
 
 // Fragments of one component held by a lane: A[jb][st4] covers pixel steps 4 st4 .. 4 st4 + 3 of
@@ -191,12 +215,15 @@ __device__ __forceinline__ TileState read_state(const float* st) {
 }
 
 // l = c_k - q / 2 for the two 16-patch halves of a tile, then the branch-free update of the state.
-template <int MODE>
+// PN = PATCH_NORM_STD: plus the residual of c_k (const_k[K + k], jd_gmm_set_const_residual) -- standardized patches are
+// small, l is the difference of two numbers several times its size, and the rounding of a float32 c_k shows in it.
+template <int MODE, int PN = PATCH_NORM_SUBTRACT_MEAN>
 __device__ __forceinline__ void finish_tile(const f32x4 (&acc)[4][2], const TileState& ts, float* st, float ck, int k,
                                             const GmmFwdArgs& a, int n_first, bool writer) {
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
-    const float l = fmaf(-0.5f, sum_lane_groups(sum_squares(acc, nb)), ck);  // gmm.py:276-281
+    float l = fmaf(-0.5f, sum_lane_groups(sum_squares(acc, nb)), ck);  // gmm.py:276-281
+    if constexpr (PN == PATCH_NORM_STD) l += a.const_k[a.K + k];
     float* s0 = st + nb * 16;
     if (MODE == MODE_MAX) {
       const bool better = l > ts.b[nb];  // strict: the lowest component wins a tie, like torch.max
@@ -218,7 +245,7 @@ __device__ __forceinline__ void finish_tile(const f32x4 (&acc)[4][2], const Tile
 // One component over the block's TB tiles, software pipelined by hand: while the MFMAs of tile t
 // issue, the wave has the B operands of tile t+1 in flight from LDS and finishes tile t-1 in the VALU
 // shadow of the matrix pipe.  Every stage is one basic block (no branches), TB is even and >= 4.
-template <int TB, int MODE, bool TRI>
+template <int TB, int MODE, bool TRI, int PN = PATCH_NORM_SUBTRACT_MEAN>
 __device__ __forceinline__ void sweep_tiles(const FragBuf& f, const float* xs_lane, float* st_lane, float ck, int k,
                                             const GmmFwdArgs& a, int n_lane, bool writer) {
   static_assert(TB >= 4 && TB % 2 == 0, "TB must be even and >= 4");
@@ -231,17 +258,17 @@ __device__ __forceinline__ void sweep_tiles(const FragBuf& f, const float* xs_la
     const TileState s0 = read_state<MODE>(st_lane + (t - 1) * 64);
     load_x(x0, xs_lane, t + 1);
     mfma_tile<TRI>(acc1, f, x1);
-    finish_tile<MODE>(acc0, s0, st_lane + (t - 1) * 64, ck, k, a, n_lane + 32 * (t - 1), writer);
+    finish_tile<MODE, PN>(acc0, s0, st_lane + (t - 1) * 64, ck, k, a, n_lane + 32 * (t - 1), writer);
     const TileState s1 = read_state<MODE>(st_lane + t * 64);
     load_x(x1, xs_lane, t + 2);  // t + 2 <= TB - 1
     mfma_tile<TRI>(acc0, f, x0);
-    finish_tile<MODE>(acc1, s1, st_lane + t * 64, ck, k, a, n_lane + 32 * t, writer);
+    finish_tile<MODE, PN>(acc1, s1, st_lane + t * 64, ck, k, a, n_lane + 32 * t, writer);
   }
   const TileState s0 = read_state<MODE>(st_lane + (TB - 2) * 64);
   const TileState s1 = read_state<MODE>(st_lane + (TB - 1) * 64);
   mfma_tile<TRI>(acc1, f, x1);
-  finish_tile<MODE>(acc0, s0, st_lane + (TB - 2) * 64, ck, k, a, n_lane + 32 * (TB - 2), writer);
-  finish_tile<MODE>(acc1, s1, st_lane + (TB - 1) * 64, ck, k, a, n_lane + 32 * (TB - 1), writer);
+  finish_tile<MODE, PN>(acc0, s0, st_lane + (TB - 2) * 64, ck, k, a, n_lane + 32 * (TB - 2), writer);
+  finish_tile<MODE, PN>(acc1, s1, st_lane + (TB - 1) * 64, ck, k, a, n_lane + 32 * (TB - 1), writer);
 }
 
 // LDS index (in floats) of pixel p of patch c of tile t in B-fragment order:
@@ -315,9 +342,17 @@ __device__ __forceinline__ void whiten_columns(f32x4 (&y)[4][2], const float (&x
 // G^T = P'_k Y^T (k-step (jb, r) feeds lane group g the value y[jb][nb][r]), gamma = -G, minus its mean over the 64
 // pixels (adjoint of the mean subtraction); lane (g, n16) writes pixels 16 ib + 4 g + (0..3) of patch (nb, n16) to
 // rows[nb] where valid[nb].  The columns (patches) of the MFMA are independent: zero columns change nothing.
-template <bool TRI>
+// PN = PATCH_NORM_STD: the adjoint of the standardized norm instead (standardized_row_offset), with the kernel's
+// arguments `a` and the patches' grid positions and means `sp`.
+struct StdPatch {
+  int py, px;
+  float mean;
+};
+
+template <bool TRI, int PN = PATCH_NORM_SUBTRACT_MEAN, class Args = void>
 __device__ __forceinline__ void patch_gradient_rows(const f32x4 (&y)[4][2], const float* gfrag, int k, int lane,
-                                                    const bool (&valid)[2], float* const (&rows)[2]) {
+                                                    const bool (&valid)[2], float* const (&rows)[2], const Args* a = nullptr,
+                                                    const StdPatch* sp = nullptr) {
   const int g = lane >> 4;
   f32x4 gacc[4][2];
   const float4* gk = reinterpret_cast<const float4*>(gfrag) + (size_t)k * (AFRAG_FLOATS / 4) + lane;
@@ -341,7 +376,17 @@ __device__ __forceinline__ void patch_gradient_rows(const f32x4 (&y)[4][2], cons
 #pragma unroll
     for (int ib = 0; ib < 4; ++ib) sum += (gacc[ib][nb][0] + gacc[ib][nb][1]) + (gacc[ib][nb][2] + gacc[ib][nb][3]);
     const float mean = sum_lane_groups(sum) * (1.f / 64.f);
-    if (valid[nb]) {
+    if constexpr (PN == PATCH_NORM_STD) {
+      const float m = sp[nb].mean;
+      const float c = standardized_row_offset(*a, sp[nb].py, sp[nb].px, g, m, mean, [&](int ib, int e) { return gacc[ib][nb][e]; });
+      if (valid[nb]) {
+        float4* out = reinterpret_cast<float4*>(rows[nb]);
+#pragma unroll
+        for (int ib = 0; ib < 4; ++ib)
+          out[4 * ib + g] = make_float4((c - gacc[ib][nb][0]) / m, (c - gacc[ib][nb][1]) / m, (c - gacc[ib][nb][2]) / m,
+                                        (c - gacc[ib][nb][3]) / m);
+      }
+    } else if (valid[nb]) {
       float4* out = reinterpret_cast<float4*>(rows[nb]);
 #pragma unroll
       for (int ib = 0; ib < 4; ++ib)
@@ -637,6 +682,7 @@ struct GmmPass {  // a pass between its two phases (gmm_prior_impl): what the ga
   int gen = 0;
   const int* shift_dev = nullptr;
   ImageNormArgs norm{};  // image norm of its phase 1 (the gather's chain rule must be that norm's)
+  int patch_norm = PATCH_NORM_SUBTRACT_MEAN;  // patch norm of its phase 1 (the rows are that norm's)
 };
 
 }  // namespace jd
@@ -646,6 +692,7 @@ struct jd_gmm {
   jd::Gmm256* d256 = nullptr;  // a D = 256 handle: everything but the image norm lives in gmm256.hip
   jd::GmmPass pass;
   jd::ImageNormArgs norm{};  // image norm the next prior call takes (jd_gmm_set_image_norm; kind 0 = identity)
+  int patch_norm = jd::PATCH_NORM_SUBTRACT_MEAN;  // patch norm the next prior call takes (jd_gmm_set_patch_norm)
   jd::DevBuf<float> normed;  // n(flux) of the pass, (H, W): what phase 1 reads in place of the flux
   int K = 0;
   bool triangular = true;  // every P_k upper triangular -> zero blocks are skipped
@@ -713,10 +760,13 @@ namespace jd {
 // gmm_dense.hip.  launch_fwd: gmm_fwd_kernel in mode MODE_MAX | MODE_LSE | MODE_DENSE, one fp64 partial sum per block
 // (*n_partials = number of blocks), under its own profile scope; launch_fwd_blocks: the same launch without the scope
 // and without the JD_GMM_DENSE override (the gated fallback of the screened path).
-int launch_fwd(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStream_t s, int* n_partials);
-int launch_fwd_blocks(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStream_t s, int* n_partials);
-void launch_bwd_max(const GmmBwdArgs& b, bool tri, unsigned blocks, hipStream_t s);
-void launch_bwd_lse(const GmmBwdLseArgs& b, bool tri, unsigned blocks, hipStream_t s);
+// patch_norm: PATCH_NORM_* of the pass (MODE_DENSE takes finished patches and has none).
+int launch_fwd(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStream_t s, int* n_partials,
+               int patch_norm = PATCH_NORM_SUBTRACT_MEAN);
+int launch_fwd_blocks(int mode, const GmmFwdArgs& a, bool tri, int n_cu, hipStream_t s, int* n_partials,
+                      int patch_norm = PATCH_NORM_SUBTRACT_MEAN);
+void launch_bwd_max(const GmmBwdArgs& b, bool tri, unsigned blocks, hipStream_t s, int patch_norm = PATCH_NORM_SUBTRACT_MEAN);
+void launch_bwd_lse(const GmmBwdLseArgs& b, bool tri, unsigned blocks, hipStream_t s, int patch_norm = PATCH_NORM_SUBTRACT_MEAN);
 // gmm_sort.hip: count -> binscan -> scatter over `chunks` blocks
 void launch_bucket_sort(const GmmBucketArgs& bk, unsigned chunks, hipStream_t s);
 // gmm_screen.hip (see there)

@@ -388,7 +388,10 @@ class GmmHandle:
     """GMM constants in MFMA fragment order on the device (jd_gmm)."""
 
     def __init__(self, precisions_cholesky, means_precisions_cholesky, log_det_cholesky, log_weights,
-                 pixel_weights, device):
+                 pixel_weights, device, const_float64=None):
+        """``const_float64``: the per-component constants -D/2 log(2 pi) + log|P_k| + log pi_k evaluated in float64 (K,);
+        what the float32 constants below lose of them goes to the library as well (jd_gmm_set_const_residual) and
+        enters the passes under the standardized patch norm, whose values are small differences of large terms."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("GmmHandle needs a HIP device (no CPU fallback)")
@@ -409,6 +412,12 @@ class GmmHandle:
         with torch.cuda.device(self.device):
             check(_hip.lib().jd_gmm_create(K, D, as_fp(pc), as_fp(mp), as_fp(const_k), as_fp(pw), ctypes.byref(handle)))
         self._handle = handle
+        if const_float64 is not None:
+            residual = np.ascontiguousarray(np.asarray(const_float64, dtype=np.float64) - const_k.astype(np.float64), dtype=np.float32)
+            if residual.shape != (K,):
+                raise ValueError(f"const_float64 must hold one value per component, got shape {residual.shape}")
+            with torch.cuda.device(self.device):
+                check(_hip.lib().jd_gmm_set_const_residual(handle, as_fp(residual)))
 
     def close(self):
         if self._handle is not None:
@@ -431,14 +440,25 @@ class GmmHandle:
         data = _hip.ImageNormStruct(int(kind), float(p0), float(p1))
         check(_hip.lib().jd_gmm_set_image_norm(self._handle, ctypes.byref(data)))
 
+    def set_patch_norm(self, patch_norm):
+        """Hand the patch norm of the NEXT prior call to the library (jd_gmm_set_patch_norm); like the image norm it is a
+        state of the shared handle, so every prior call sets it anew.  ``patch_norm``: a `PatchNorm` with a device kind, or
+        None = subtract-mean."""
+        kind = 0 if patch_norm is None else patch_norm.device_kind
+        if kind is None:
+            raise NotImplementedError(f"patch norm {type(patch_norm).__name__} has no HIP kernel")
+        check(_hip.lib().jd_gmm_set_patch_norm(self._handle, int(kind)))
+
     def prior_fwd_bwd(self, flux, stride, shifts, value_out, value_scale, grad=None, grad_coef=0.0,
                       marginalize=False, patch_rows=(0, -1), accumulate_value=False, argmax_out=None, band_out=None, phases=3,
-                      norm=None):
+                      norm=None, patch_norm=None):
         """``band_out``: instead of accumulating into ``grad``, write the gradient of the patch rows ``patch_rows`` as the
         band of the rolled frame they cover (jd_gmm_prior_band_fwd_bwd; `band_rows` gives its extent).
-        ``norm``: the prior's image norm (None = identity); the gradient is the one with respect to the raw flux."""
+        ``norm``: the prior's image norm (None = identity); the gradient is the one with respect to the raw flux.
+        ``patch_norm``: the prior's patch norm (None = subtract-mean)."""
         flux = require_hip_tensor(flux, "flux")
         self.set_image_norm(norm)
+        self.set_patch_norm(patch_norm)
         H, W = flux.shape[-2:]
         if flux.numel() != H * W:
             raise ValueError("flux must be a single (H, W) image")
@@ -471,12 +491,13 @@ class GmmHandle:
         )
 
     def prior_fwd_bwd_step(self, flux, stride, shifts, value_out, value_scale, grad_coef, step, marginalize=False,
-                           accumulate_value=False, phases=3, norm=None):
+                           accumulate_value=False, phases=3, norm=None, patch_norm=None):
         """The whole prior with the component's optimizer step in the epilogue of its gather kernel
         (jd_gmm_prior_fwd_bwd_step; ``step``: a filled `_hip.Step`).  Raises RuntimeError where the library does not
         support it (stride < 4): the caller then evaluates the prior and steps separately."""
         flux = require_hip_tensor(flux, "flux")
         self.set_image_norm(norm)
+        self.set_patch_norm(patch_norm)
         H, W = flux.shape[-2:]
         shift_dev = None
         if isinstance(shifts, DeviceShifts):
@@ -561,7 +582,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     """Scalar GMM patch log-prior with its HIP gradient (priors/patches/core.py:227-246)."""
 
     @staticmethod
-    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None):
+    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None, patch_norm=None):
         image = require_hip_tensor(flux, "flux")
         value = torch.empty(1, dtype=torch.float32, device=image.device)
         grad = None
@@ -569,7 +590,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
             grad = torch.zeros(image.shape[-2:], dtype=torch.float32, device=image.device)
         handle.prior_fwd_bwd(
             image.reshape(image.shape[-2:]), stride, shifts, value, value_scale, grad=grad, grad_coef=value_scale,
-            marginalize=marginalize, norm=norm,
+            marginalize=marginalize, norm=norm, patch_norm=patch_norm,
         )
         ctx.grad, ctx.shape = grad, flux.shape
         return value.reshape(())
@@ -577,7 +598,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_value):
         # (ctx.grad is the finished gradient with respect to the raw flux: the library applied the norm's chain rule)
-        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None
+        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None, None
 
 
 def elementwise_prior_subpix(kind, flux, alpha, beta, log_const, shifts, value_out, grad_coef, grad=None):

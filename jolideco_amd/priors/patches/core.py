@@ -18,8 +18,13 @@ class GMMPatchPrior(Prior):
 
     Same constructor as the reference.  8x8 and 16x16 patches (64 / 256 features) have kernels; a 16x16 prior runs the
     whole-image dense pass only (`shardable`, `supports_fused_step`, `supports_phases` are False for it).  Options that are not on the accelerated path
-    (``cycle_spin_subpix``, ``jitter``, other patch norms) raise
+    (``cycle_spin_subpix``, ``jitter``) raise
     NotImplementedError instead of silently running something else.
+
+    ``patch_norm``: `SubtractMeanPatchNorm` or `StandardizedSubtractMeanPatchNorm` (relative contrast, (p - mean) / mean),
+    by default the one the mixture was trained with (``gmm.meta.patch_norm``, the ``PNPTYPE`` keyword of a table file).
+    Both are fused into the kernels.  The standardized norm always takes the dense fp32 kernels -- the fp16 screen of the
+    8x8 path is derived for mean-free patches and is not used for it -- and has no ``compute_error`` (`hessian_ones`).
 
     ``norm``: identity, asinh, fixed-max, sigmoid, atan, log or power image norm (`utils.norms`), applied on the device in
     front of the patch extraction; the gradient is the one with respect to the raw flux.  The norm's parameters are
@@ -63,8 +68,8 @@ class GMMPatchPrior(Prior):
             raise NotImplementedError(f"image norm {type(norm).__name__} is not implemented in jolideco_amd")
         self.norm = norm
         patch_norm = patch_norm if patch_norm is not None else gmm.meta.patch_norm
-        if not isinstance(patch_norm, SubtractMeanPatchNorm):
-            raise NotImplementedError("only SubtractMeanPatchNorm is implemented in jolideco_amd")
+        if not isinstance(patch_norm, PatchNorm) or patch_norm.device_kind is None:
+            raise NotImplementedError(f"patch norm {type(patch_norm).__name__} is not implemented in jolideco_amd")
         self.patch_norm = patch_norm
         self.marginalize = marginalize
         self.device = torch.device(device)
@@ -127,7 +132,7 @@ class GMMPatchPrior(Prior):
         shifts = self.draw_shifts()
         scale = self.log_like_weight / flux.numel()
         return GMMPatchPriorFunction.apply(
-            flux, self.gmm.handle(flux.device), self.stride, shifts, self.marginalize, scale, self.norm
+            flux, self.gmm.handle(flux.device), self.stride, shifts, self.marginalize, scale, self.norm, self.patch_norm
         )
 
     def device_fwd_bwd(self, flux, value_out, grad=None, coef=0.0, patch_rows=None, shifts="draw", band_out=None, phases=3):
@@ -139,6 +144,7 @@ class GMMPatchPrior(Prior):
         self.gmm.handle(flux.device).prior_fwd_bwd(
             flux.reshape(flux.shape[-2:]), self.stride, shifts, value_out, scale, grad=grad, grad_coef=coef * scale,
             marginalize=self.marginalize, patch_rows=patch_rows or (0, -1), band_out=band_out, phases=phases, norm=self.norm,
+            patch_norm=self.patch_norm,
         )
 
     def device_fwd_bwd_step(self, flux, value_out, coef, step, shifts="draw", phases=3):
@@ -150,15 +156,27 @@ class GMMPatchPrior(Prior):
         scale = self.log_like_weight / flux.numel()
         self.gmm.handle(flux.device).prior_fwd_bwd_step(
             flux.reshape(flux.shape[-2:]), self.stride, shifts, value_out, scale, coef * scale, step,
-            marginalize=self.marginalize, phases=phases, norm=self.norm,
+            marginalize=self.marginalize, phases=phases, norm=self.norm, patch_norm=self.patch_norm,
         )
 
     def hessian_ones(self, flux):
         """Every patch has its mean subtracted before the mixture sees it, so a constant vector is in the null
         space of each patch's quadratic form: Hessian x ones is exactly zero (the reference's double backward
-        returns rounding noise there).  One pair of shifts is drawn, as the reference's evaluation does."""
+        returns rounding noise there).  One pair of shifts is drawn, as the reference's evaluation does.
+        The argument holds for `SubtractMeanPatchNorm` only: under the standardized norm a constant added to a patch
+        changes x = (p - m) / m, and there is no kernel for that Hessian product."""
+        self.check_hessian_ones()
         self.draw_shifts()
         return torch.zeros_like(flux)
+
+    def check_hessian_ones(self):
+        """Raise where `hessian_ones` (``compute_error=True``) is not available: any patch norm but subtract-mean."""
+        if not isinstance(self.patch_norm, SubtractMeanPatchNorm):
+            name = self.patch_norm.to_dict().get("type", type(self.patch_norm).__name__)
+            raise NotImplementedError(
+                f"compute_error=True is not implemented for a GMMPatchPrior with patch norm {name!r}: the Hessian "
+                "product with ones is zero for 'subtract-mean' only"
+            )
 
     def n_patch_rows(self, shape):
         return (shape[-2] - self.patch_shape[0]) // self.stride + 1

@@ -177,6 +177,15 @@ class GaussianMixtureModel:
         return torch.sum(torch.log(diag), axis=1).numpy()
 
     @property
+    def const_float64_numpy(self):
+        """-D/2 log(2 pi) + sum_i log P_k[i, i] + log pi_k of the float32 factors and weights, evaluated in float64 (K,):
+        the constants of `estimate_log_prob` without the roundings of their float32 sum (`ops.GmmHandle`)."""
+        pc = self.precisions_cholesky_numpy.astype(np.float64)
+        diag = pc.reshape(self.n_components, -1)[:, :: self.n_features + 1]
+        log_weights = np.log(self.weights_numpy.astype(np.float64))
+        return -0.5 * self.n_features * np.log(2 * np.pi) + np.log(diag).sum(axis=1) + log_weights
+
+    @property
     def log_weights_numpy(self):
         return torch.log(torch.from_numpy(self.weights_numpy)).numpy()
 
@@ -206,6 +215,7 @@ class GaussianMixtureModel:
                 log_weights=self.log_weights_numpy,
                 pixel_weights=self.pixel_weights_numpy.astype(np.float32),
                 device=device,
+                const_float64=self.const_float64_numpy,
             )
         return self._handles[key]
 

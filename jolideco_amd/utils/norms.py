@@ -4,7 +4,8 @@ Image norms (reference jolideco/utils/norms.py:225-426): identity, asinh, fixed-
 the device the norm is one streaming pass in front of the patch kernels and its derivative rides in the gather kernel
 (csrc/gmm_gather.hip); the classes here carry the parameters, the plain-torch evaluation (any device) and the (de)serialisation.
 ``"max"`` (a global reduction) and ``"inverse-cdf"`` (a table lookup) are not implemented and raise NotImplementedError.
-Patch norms: `SubtractMeanPatchNorm` (:97-103, fused into the HIP kernel).
+Patch norms (:97-112): `SubtractMeanPatchNorm` and `StandardizedSubtractMeanPatchNorm`, both fused into the dense HIP
+kernels (`device_kind` selects the instantiation, jd_gmm_set_patch_norm).
 """
 import numpy as np
 import torch
@@ -12,6 +13,7 @@ import torch
 __all__ = [
     "PatchNorm",
     "SubtractMeanPatchNorm",
+    "StandardizedSubtractMeanPatchNorm",
     "ImageNorm",
     "IdentityImageNorm",
     "ASinhImageNorm",
@@ -27,6 +29,9 @@ __all__ = [
 
 class PatchNorm:
     """Patch normalisation base class"""
+
+    #: kind of `jd_gmm_set_patch_norm` (include/jolideco_hip.h); None: no device kernel
+    device_kind = None
 
     def to_dict(self):
         for name, cls in NORMS_PATCH_REGISTRY.items():
@@ -49,8 +54,22 @@ class SubtractMeanPatchNorm(PatchNorm):
     """Subtract the patch mean (Zoran & Weiss).  On device this is fused into the GMM kernel
     (csrc/gmm_gather.hip); this host version works on torch tensors for explicit patch arrays."""
 
+    device_kind = 0
+
     def __call__(self, patches):
         return patches - patches.nanmean(dim=1, keepdim=True)
+
+
+class StandardizedSubtractMeanPatchNorm(PatchNorm):
+    """Relative contrast of a patch: subtract the patch mean, then divide by it (reference utils/norms.py:106-112).  On
+    the device it is fused into the dense fp32 GMM kernels (csrc/gmm_dense.hip, csrc/gmm256.hip), which a prior with
+    this norm always takes; this host version works on torch tensors for explicit patch arrays."""
+
+    device_kind = 1
+
+    def __call__(self, patches):
+        patches_mean = patches.nanmean(dim=1, keepdim=True)
+        return (patches - patches_mean) / patches_mean
 
 
 class ImageNorm:
@@ -293,4 +312,7 @@ NORMS_REGISTRY = {
     "power": PowerImageNorm,
     "identity": IdentityImageNorm,
 }
-NORMS_PATCH_REGISTRY = {"subtract-mean": SubtractMeanPatchNorm}
+NORMS_PATCH_REGISTRY = {
+    "std-subtract-mean": StandardizedSubtractMeanPatchNorm,
+    "subtract-mean": SubtractMeanPatchNorm,
+}
