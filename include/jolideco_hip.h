@@ -586,6 +586,33 @@ int jd_sparse_backward(const float* param_flux, const float* x_pos, const float*
                        int W, const float* grad_flux_image, float* grad_param, float* grad_x, float* grad_y,
                        void* stream);
 
+/* Pyramid of the multi-scale prior (priors/patches/core.py:303-324) -----------------------------------------------
+ * Per level l, f = 2^l, the reference blurs the running image with a sampled Gaussian ("same", zero padded, cumulative:
+ * core.py:316-320, `convolve_fft_torch`), takes f x f means (core.py:322, `F.avg_pool2d`: ragged rows / columns are
+ * dropped) and hands them to the inner prior; autograd runs the chain backwards.  `taps`: HOST array of the n_taps
+ * (odd, <= 43) factors u of the kernel K = u u^T, passed to the kernels by value; n_taps = 1 with u = {1} is no blur.
+ *
+ * jd_multiscale_down (one launch): g_out (H, W) <- K (*) src (skipped when NULL), d_out (H / f, W / f) <- the f x f
+ * means of it, dd_zero (same shape, optional) <- 0.  The loads read src rolled by (shift_y, shift_x), both reduced modulo
+ * the shape: rolled[y, x] = src[(y - shift_y) mod H, (x - shift_x) mod W] (core.py:303-308, `cycle_spin`).  The means
+ * are summed in a fixed order without atomics: run-to-run identical.
+ *
+ * jd_multiscale_up_adjoint (one launch): out <- K^T (*) (dg + replicate_f(dd) / f^2); dg (H, W) may be NULL (the last
+ * level).  rolled = 0: out (H, W) is assigned.  rolled = 1: out is the gradient image of the un-rolled flux and
+ * out[(y - shift_y) mod H, (x - shift_x) mod W] += the result at [y, x].  With value_out the launch also writes
+ * value_out[0] = sum_i level_coefs[i] * level_values[i] (i < n_values <= JD_MULTISCALE_MAX_LEVELS; level_values: device,
+ * level_coefs: host; float32, index order: core.py:324).  jd_multiscale_value: that sum alone (a forward-only call).
+ *
+ * JD_ERR_INVALID, before anything reaches a device: null pointers, f not in {1, 2, 4, 8, 16}, an even number of taps or
+ * more than 43, an image smaller than f, shifts outside [0, H) x [0, W), g_out == src or out == dg. */
+#define JD_MULTISCALE_MAX_LEVELS 5
+int jd_multiscale_down(const float* src, int H, int W, int f, const float* taps, int n_taps, int shift_y, int shift_x,
+                       float* g_out, float* d_out, float* dd_zero, void* stream);
+int jd_multiscale_up_adjoint(const float* dg, const float* dd, int H, int W, int f, const float* taps, int n_taps,
+                             float* out, int rolled, int shift_y, int shift_x, const float* level_values,
+                             const float* level_coefs, int n_values, float* value_out, void* stream);
+int jd_multiscale_value(const float* level_values, const float* level_coefs, int n_values, float* value_out, void* stream);
+
 /* Kernel timers -----------------------------------------------------------------------------
  * New (the reference has no profiler hooks).  After jd_profile_enable(n) the
  * library brackets every launch of the kernels below with a hipEvent pair on the launch stream
@@ -616,7 +643,9 @@ enum {
   JD_KERNEL_ELEMENTWISE_PRIOR = 20, /* element-wise priors (inverse-gamma, exponential): value + gradient */
   JD_KERNEL_SPARSE_RENDER = 21,  /* sparse component: zero fill + one thread per (source, tap), index-ordered sums */
   JD_KERNEL_SPARSE_BACKWARD = 22, /* sparse component: gradients of flux and positions from the <= 4 taps of a source */
-  JD_KERNEL_COUNT = 23
+  JD_KERNEL_MULTISCALE_DOWN = 23, /* multi-scale prior: blur + f x f means of one level */
+  JD_KERNEL_MULTISCALE_UP = 24,  /* multi-scale prior: adjoint of both (replicate + correlate) */
+  JD_KERNEL_COUNT = 25
 };
 int jd_profile_enable(int capacity);
 int jd_profile_disable(void);

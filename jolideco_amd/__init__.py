@@ -19,6 +19,7 @@ from .priors import (
     GaussianMixtureModel,
     GMMPatchPrior,
     InverseGammaPrior,
+    MultiScalePrior,
     Priors,
     SmoothnessPrior,
     UniformPrior,
@@ -41,6 +42,7 @@ __all__ = [
     "NPredCalibrations",
     "GaussianMixtureModel",
     "GMMPatchPrior",
+    "MultiScalePrior",
     "UniformPrior",
     "InverseGammaPrior",
     "ExponentialPrior",

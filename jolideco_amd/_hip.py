@@ -144,6 +144,15 @@ EXPORTS = {
     "jd_sparse_backward": (
         c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "jd_multiscale_down": (
+        c_int, [c_void_p, c_int, c_int, c_int, fp, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "jd_multiscale_up_adjoint": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int, c_int, fp, c_int, c_void_p, c_int, c_int, c_int, c_void_p, fp, c_int, c_void_p,
+         c_void_p],
+    ),
+    "jd_multiscale_value": (c_int, [c_void_p, fp, c_int, c_void_p, c_void_p]),
     "jd_profile_enable": (c_int, [c_int]),
     "jd_profile_disable": (c_int, []),
     "jd_profile_pause": (c_int, [c_int]),
@@ -178,7 +187,7 @@ KERNEL_IDS = {
     "adjoint_epilogue": 6, "adam": 7, "fft_r2c": 8, "fft_c2r": 9, "direct_conv": 10, "sep_conv": 11,
     "gmm_screen": 12, "gmm_sort": 13, "gmm_exact": 14, "gmm_stage": 15, "shift": 16,
     "poisson_mixed": 17, "elementwise_subpix": 18, "smoothness": 19, "elementwise_prior": 20,
-    "sparse_render": 21, "sparse_backward": 22,
+    "sparse_render": 21, "sparse_backward": 22, "multiscale_down": 23, "multiscale_up": 24,
 }
 
 _lib = None

@@ -603,6 +603,15 @@ class FitSession:
                 f"checkpoints are ASDF files, which cannot carry the sparse flux component {sparse[0]!r}: fit without "
                 "checkpoint_path and write the result in the FITS format"
             )
+        multiscale = [name for name, c in components.items() if getattr(getattr(c, "prior", None), "shift_kind", None) == "levels"]
+        # (a draw of a multi-scale prior is one pair per level, on grids of different sizes: by-value epochs only)
+        self.has_multiscale = bool(multiscale)
+        if multiscale and deconvolver.checkpoint_path is not None:
+            prior = components[multiscale[0]].prior
+            raise NotImplementedError(
+                f"checkpoints are ASDF files, which cannot carry the {type(prior).__name__} of the flux component "
+                f"{multiscale[0]!r}: fit without checkpoint_path"
+            )
         device = deconvolver.device
         self.components = components = components.to(device)
         self.joint = deconvolver.fit_mode == "joint"
@@ -913,8 +922,9 @@ class FitSession:
     def _planned_capable(self):
         """Planned epochs apply: one process, the session's own optimizer step (a hook sees every gradient through the
         by-value path), no event brackets around collectives, no kernel timers, no sparse component (its stepper takes
-        its bias terms by value: by-value epochs only, nothing is captured)."""
-        if self.has_sparse:
+        its bias terms by value: by-value epochs only, nothing is captured) and no multi-scale prior (a draw is one pair
+        per level on grids of different sizes: a captured epoch would bake them in)."""
+        if self.has_sparse or getattr(self, "has_multiscale", False):
             return False
         cfg = self.cfg
         own = getattr(type(cfg), "_optimizer_step", None) is MAPDeconvolver._optimizer_step and "_optimizer_step" not in vars(cfg)
@@ -1520,9 +1530,10 @@ def _write_map_result_to_npz(result, filename, overwrite):
     filename = Path(filename)
     if filename.exists() and not overwrite:
         raise OSError(f"{filename} exists")
-    from .utils.io.asdf import refuse_sparse
+    from .utils.io.asdf import refuse_multiscale, refuse_sparse
 
     refuse_sparse(result.components, "an npz result")
+    refuse_multiscale(result.components, "an npz result")
     arrays = {f"flux/{name}": flux for name, flux in result.components.to_numpy().items()}
     for name, component in result.components.items():
         arrays[f"meta/{name}"] = np.array(

@@ -163,6 +163,8 @@ extern "C" const char* jd_kernel_name(int kernel) {
     case JD_KERNEL_ELEMENTWISE_PRIOR: return "elementwise_prior_kernel";
     case JD_KERNEL_SPARSE_RENDER: return "sparse_render_kernel";
     case JD_KERNEL_SPARSE_BACKWARD: return "sparse_backward_kernel";
+    case JD_KERNEL_MULTISCALE_DOWN: return "multiscale_down_kernel";
+    case JD_KERNEL_MULTISCALE_UP: return "multiscale_up_kernel";
     default: return "?";
   }
 }

@@ -739,6 +739,71 @@ class SparseRenderFunction(torch.autograd.Function):
         return grads[0], grads[1], grads[2], None, None
 
 
+MULTISCALE_MAX_LEVELS = 5  # JD_MULTISCALE_MAX_LEVELS of include/jolideco_hip.h
+MULTISCALE_FACTORS = (1, 2, 4, 8, 16)
+
+
+def _host_floats(values):
+    """(ctypes float array, length) of a short host vector (the taps of a level, the level coefficients)."""
+    values = [float(v) for v in values]
+    return (c_float * len(values))(*values), len(values)
+
+
+def multiscale_down(src, f, taps, d_out, g_out=None, dd_zero=None, shifts=None):
+    """One level of the multi-scale pyramid (jd_multiscale_down): ``g_out`` <- K (*) ``src`` (K = outer(taps, taps), "same",
+    zero padded; None: not stored), ``d_out`` <- its ``f`` x ``f`` means (floor), ``dd_zero`` <- 0.  ``shifts``: the loads
+    read ``src`` rolled by this pair (rows, columns), as `torch.roll` would."""
+    src = require_hip_tensor(src, "src")
+    H, W = src.shape[-2:]
+    sy, sx = (0, 0) if shifts is None else (int(shifts[0]) % H, int(shifts[1]) % W)
+    if tuple(d_out.shape[-2:]) != (H // f, W // f):
+        raise ValueError(f"d_out must have shape {(H // f, W // f)}, got {tuple(d_out.shape[-2:])}")
+    arr, n = _host_floats(taps)
+    check(_hip.lib().jd_multiscale_down(ptr(src), H, W, int(f), arr, n, sy, sx, ptr(g_out), ptr(d_out), ptr(dd_zero),
+                                        stream_ptr(src.device)))
+
+
+def multiscale_up_adjoint(dd, f, taps, out, dg=None, shifts=None, rolled=False, value=None):
+    """Adjoint of one level (jd_multiscale_up_adjoint): ``out`` <- K^T (*) (``dg`` + replicate_f(``dd``) / f^2); with
+    ``rolled`` the result is ADDED to ``out`` at the un-rolled pixel (the session's gradient image).  ``value``:
+    (level values on the device, host coefficients, value_out) -- the launch also writes their weighted sum."""
+    dd = require_hip_tensor(dd, "dd")
+    H, W = out.shape[-2:]
+    sy, sx = (0, 0) if shifts is None else (int(shifts[0]) % H, int(shifts[1]) % W)
+    if tuple(dd.shape[-2:]) != (H // f, W // f):
+        raise ValueError(f"dd must have shape {(H // f, W // f)}, got {tuple(dd.shape[-2:])}")
+    arr, n = _host_floats(taps)
+    vals, coefs, n_values, value_out = None, None, 0, None
+    if value is not None:
+        vals, (coefs, n_values), value_out = ptr(value[0]), _host_floats(value[1]), ptr(value[2])
+    check(_hip.lib().jd_multiscale_up_adjoint(ptr(dg), ptr(dd), H, W, int(f), arr, n, ptr(out), int(bool(rolled)), sy, sx,
+                                              vals, coefs, n_values, value_out, stream_ptr(out.device)))
+
+
+def multiscale_value(values, coefs, value_out):
+    """value_out <- sum_i coefs[i] * values[i] on the device (jd_multiscale_value: a forward-only multi-scale call)."""
+    arr, n = _host_floats(coefs)
+    check(_hip.lib().jd_multiscale_value(ptr(values), arr, n, ptr(value_out), stream_ptr(value_out.device)))
+
+
+class MultiScalePriorFunction(torch.autograd.Function):
+    """Scalar multi-scale log-prior with its HIP gradient (priors/patches/core.py:288-326): the prior's own device pass with
+    coefficient 1 into a fresh gradient image."""
+
+    @staticmethod
+    def forward(ctx, flux, prior, shifts):
+        image = require_hip_tensor(flux, "flux")
+        value = torch.empty(1, dtype=torch.float32, device=image.device)
+        grad = torch.zeros(image.shape[-2:], dtype=torch.float32, device=image.device) if flux.requires_grad else None
+        prior.device_fwd_bwd(image, value, grad=grad, coef=1.0, shifts=shifts)
+        ctx.grad, ctx.shape = grad, flux.shape
+        return value.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_value):
+        return (ctx.grad * grad_value).reshape(ctx.shape), None, None
+
+
 def band_rows(patch_rows, stride, H, patch=8):
     """Pixel rows [y_begin, y_end) of the rolled frame that the patch rows ``patch_rows = (begin, end)`` cover
     (``end < 0``: up to the last patch row); an empty shard covers no row."""

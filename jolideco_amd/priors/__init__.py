@@ -1,5 +1,5 @@
 from .core import ExponentialPrior, InverseGammaPrior, Prior, Priors, SmoothnessPrior, UniformPrior
-from .patches import GaussianMixtureModel, GMMPatchPrior
+from .patches import GaussianMixtureModel, GMMPatchPrior, MultiScalePrior
 
 PRIOR_REGISTRY = {
     "uniform": UniformPrior,
@@ -12,6 +12,7 @@ PRIOR_REGISTRY = {
 __all__ = [
     "GaussianMixtureModel",
     "GMMPatchPrior",
+    "MultiScalePrior",
     "ExponentialPrior",
     "UniformPrior",
     "InverseGammaPrior",

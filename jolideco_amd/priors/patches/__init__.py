@@ -1,4 +1,4 @@
-from .core import GMMPatchPrior
+from .core import GMMPatchPrior, MultiScalePrior
 from .gmm import GaussianMixtureModel, GaussianMixtureModelMeta
 
-__all__ = ["GMMPatchPrior", "GaussianMixtureModel", "GaussianMixtureModelMeta"]
+__all__ = ["GMMPatchPrior", "MultiScalePrior", "GaussianMixtureModel", "GaussianMixtureModelMeta"]

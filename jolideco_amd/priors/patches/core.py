@@ -1,14 +1,16 @@
 """GMM patch prior (reference: jolideco/priors/patches/core.py:30-246)."""
 import logging
 
+import numpy as np
 import torch
 
 from ...utils.norms import IdentityImageNorm, ImageNorm, PatchNorm, SubtractMeanPatchNorm
+from ...utils.numpy import gaussian_kernel_2d
 from ...utils.torch import TORCH_DEFAULT_DEVICE, cycle_spin_shifts, cycle_spin_shifts_many, get_default_generator
 from ..core import Prior
 from .gmm import GaussianMixtureModel
 
-__all__ = ["GMMPatchPrior"]
+__all__ = ["GMMPatchPrior", "MultiScalePrior"]
 
 log = logging.getLogger(__name__)
 
@@ -203,3 +205,199 @@ class GMMPatchPrior(Prior):
         if "patch_norm" in kwargs:
             kwargs["patch_norm"] = PatchNorm.from_dict(kwargs["patch_norm"])
         return cls(**kwargs)
+
+
+MULTISCALE_MAX_LEVELS = 5  # pooling factors 1 ... 16; the widest blur has 43 taps (JD_MULTISCALE_MAX_LEVELS)
+
+
+def multiscale_level_taps(level, anti_alias=True):
+    """The factor u (float32 values as Python floats) of the blur of ``level``: the reference convolves with
+    ``Gaussian2DKernel(sigma = 2 * 2**level / 6)`` cast to float32 (priors/patches/core.py:316-320) -- 3, 7, 11, 23, 43 pixels
+    for levels 0 ... 4, an exact outer product K = u u^T with u = K[centre, :] / sqrt(K[centre, centre]).  No blur: [1]."""
+    if not anti_alias:
+        return [1.0]
+    kernel = gaussian_kernel_2d(2 * 2**level / 6.0).astype(np.float32).astype(np.float64)
+    centre = kernel.shape[0] // 2
+    return [float(v) for v in (kernel[centre] / np.sqrt(kernel[centre, centre])).astype(np.float32)]
+
+
+class MultiScalePrior(Prior):
+    """The inner prior on a Gaussian-blurred, average-pooled pyramid of the flux (reference:
+    jolideco/priors/patches/core.py:249-337; exported there, not registered, and not registered here)::
+
+        g = flux
+        for l in range(n_levels), f = 2**l:
+            if w_l == 0: continue                       # (its blur is skipped too)
+            if anti_alias: g = K_l (*) g                # Gaussian of sigma 2 f / 6, "same", zero padded, cumulative
+            value += f**2 * w_l * prior(avg_pool2d(g, f))
+
+    Same constructor as the reference.  ``weights`` (default 1 / n_levels each) are stored as log-weights and normalised by
+    a softmax, in float32, as the reference does; they are constants of the prior here (the reference trains
+    ``_log_weights``), like the parameters of the image norms.  At most 5 levels.  ``prior``: any prior of this package with a
+    `device_fwd_bwd` except another `MultiScalePrior`.
+
+    ``cycle_spin=True`` (the default): the full-resolution flux is rolled by one draw of
+    ``cycle_spin_shifts(prior.patch_shape, prior.generator)`` in front of the levels -- what the reference's
+    ``flux, _ = cycle_spin(...)`` means.  The reference itself raises ValueError there (`cycle_spin` returns one tensor), so
+    this setting is checked against the restatement of the formula above only; ``cycle_spin=False`` is checked against
+    the reference.
+
+    The blur, the pooling and their adjoints are two HIP kernels (csrc/multiscale.hip); the levels' values are summed on
+    the device.  The work buffers (two full-resolution images, the pooled image and its gradient per level, the level
+    values) belong to the prior, per device and shape: after the first call for a shape nothing is allocated, and no call
+    synchronises with the host.  A session with this prior runs by-value epochs only; the prior is not shardable, has no
+    fused optimizer step, no phases, no ``compute_error`` and no file format.
+    """
+
+    shift_kind = "levels"  # what `draw_shifts` returns: (outer roll, one entry per level)
+    shardable = False
+    supports_fused_step = False
+    supports_phases = False
+
+    def __init__(self, prior, n_levels=2, weights=None, cycle_spin=True, anti_alias=True):
+        super().__init__()
+        if isinstance(prior, MultiScalePrior) or not isinstance(prior, Prior) or type(prior).device_fwd_bwd is Prior.device_fwd_bwd:
+            raise ValueError("the inner prior must be a prior of jolideco_amd with a device_fwd_bwd, and not a MultiScalePrior")
+        n_levels = int(n_levels)
+        if not 1 <= n_levels <= MULTISCALE_MAX_LEVELS:
+            raise ValueError(f"n_levels must be in [1, {MULTISCALE_MAX_LEVELS}], got {n_levels}")
+        self.n_levels = n_levels
+        self.cycle_spin = bool(cycle_spin)
+        self.anti_alias = bool(anti_alias)
+        self.prior = prior
+        if self.cycle_spin and not (hasattr(prior, "patch_shape") and getattr(prior, "generator", None) is not None):
+            raise ValueError("cycle_spin=True rolls by a draw of cycle_spin_shifts(prior.patch_shape, prior.generator): the "
+                             f"inner {type(prior).__name__} has no patch shape / generator")
+        if weights is None:
+            weights = torch.tensor([1 / n_levels] * n_levels)
+        weights = torch.as_tensor(weights, dtype=torch.float32).reshape(-1)
+        if weights.numel() != n_levels:
+            raise ValueError(f"{n_levels} levels need {n_levels} weights, got {weights.numel()}")
+        if not bool(torch.all(weights >= 0)) or not bool(torch.any(weights > 0)):
+            raise ValueError("weights must be non-negative and not all zero")
+        self._log_weights = torch.log(weights)  # (a constant: a plain tensor, not a Parameter)
+        self._taps = [multiscale_level_taps(level, self.anti_alias) for level in range(n_levels)]
+        self._work = {}
+        self.last_shifts = None
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state["_work"] = {}
+        return state
+
+    @property
+    def weights(self):
+        """softmax of the log-weights, float32 (priors/patches/core.py:283-286)."""
+        return torch.exp(self._log_weights) / torch.sum(torch.exp(self._log_weights))
+
+    @property
+    def patch_shape(self):
+        return self.prior.patch_shape
+
+    @property
+    def levels(self):
+        """[(level, f, f**2 * w_l as the reference's float32 product)] of the evaluated levels (w_l != 0), ascending."""
+        return [(level, 2**level, float(2**level * 2**level * w)) for level, w in enumerate(self.weights) if w != 0]
+
+    @property
+    def _inner_draws(self):
+        return hasattr(self.prior, "draw_shifts") and bool(getattr(self.prior, "draws_shifts", True))
+
+    def draw_shifts(self):
+        """One draw, in the order the reference draws: the outer roll (None when ``cycle_spin`` is off), then one entry per
+        level, ascending -- the inner prior's own draw, None for a skipped level or an inner prior that draws nothing."""
+        outer = cycle_spin_shifts(self.prior.patch_shape, self.prior.generator) if self.cycle_spin else None
+        evaluated = {level for level, _, _ in self.levels}
+        inner = tuple(self.prior.draw_shifts() if (level in evaluated and self._inner_draws) else None
+                      for level in range(self.n_levels))
+        self.last_shifts = (outer,) + inner
+        return self.last_shifts
+
+    def draw_shifts_many(self, n):
+        return [self.draw_shifts() for _ in range(n)]
+
+    def _buffers_for(self, flux):
+        H, W = flux.shape[-2:]
+        key = (str(flux.device), H, W)
+        work = self._work.get(key)
+        if work is None:
+            patch = getattr(self.prior, "patch_shape", None)
+            for level in range(self.n_levels):
+                f = 2**level
+                small = (H // f < 1 or W // f < 1) if patch is None else (H // f < patch[0] or W // f < patch[1])
+                if small:
+                    raise ValueError(f"level {level} of a {H} x {W} image is {H // f} x {W // f}: smaller than "
+                                     f"{'one pixel' if patch is None else f'the inner patch {tuple(patch)}'}")
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=flux.device)  # noqa: E731
+            work = self._work[key] = {
+                "full": [new(H, W), new(H, W)],
+                "d": [new(H // 2**level, W // 2**level) for level in range(self.n_levels)],
+                "dd": [new(H // 2**level, W // 2**level) for level in range(self.n_levels)],
+                "values": new(self.n_levels),
+            }
+        return work
+
+    def __call__(self, flux):
+        """Differentiable log-prior of a (1, 1, H, W) HIP tensor; draws once (`draw_shifts`)."""
+        from ...ops import MultiScalePriorFunction
+
+        return MultiScalePriorFunction.apply(flux, self, self.draw_shifts())
+
+    def device_fwd_bwd(self, flux, value_out, grad=None, coef=0.0, shifts="draw", patch_rows=None):
+        """Fused path: value -> device scalar, ``grad += coef * d logprior / d flux``.  ``shifts``: a draw of `draw_shifts`
+        ("draw": drawn now).  The factors f**2 * w_l * coef travel as the inner prior's coefficient, so the pooled
+        gradients arrive scaled; the weighted sum of the level values is formed on the device."""
+        from ...ops import multiscale_down, multiscale_up_adjoint, multiscale_value
+
+        if isinstance(shifts, str):
+            shifts = self.draw_shifts()
+        outer, inner_shifts = shifts[0], shifts[1:]
+        image = flux.reshape(flux.shape[-2:])
+        work = self._buffers_for(image)
+        levels = self.levels
+        values = work["values"][: len(levels)]
+        with_grad = grad is not None
+        src = image
+        for i, (level, f, level_coef) in enumerate(levels):
+            last = i == len(levels) - 1
+            g_out = None if last else work["full"][i % 2]
+            d, dd = work["d"][level], work["dd"][level]
+            multiscale_down(src, f, self._taps[level], d, g_out=g_out, dd_zero=dd if with_grad else None,
+                            shifts=outer if i == 0 else None)
+            kwargs = {"shifts": inner_shifts[level]} if self._inner_draws else {}
+            self.prior.device_fwd_bwd(d.reshape((1, 1) + tuple(d.shape)), values[i : i + 1], grad=dd if with_grad else None,
+                                      coef=coef * level_coef if with_grad else 0.0, **kwargs)
+            src = g_out
+        coefs = [level_coef for _, _, level_coef in levels]
+        if not with_grad:
+            multiscale_value(values, coefs, value_out)
+            return
+        dg = None
+        for i in range(len(levels) - 1, -1, -1):
+            level, f, _ = levels[i]
+            first = i == 0
+            # (g_out of level i lived in full[i % 2] and is dead by now: dg_{i-1} goes to the image the level READ, never to
+            # the one it takes dg_i from)
+            out = grad.reshape(grad.shape[-2:]) if first else work["full"][(i + 1) % 2]
+            multiscale_up_adjoint(work["dd"][level], f, self._taps[level], out, dg=dg, rolled=first,
+                                  shifts=outer if first else None, value=(values, coefs, value_out) if first else None)
+            dg = out
+
+    def hessian_ones(self, flux):
+        self.check_hessian_ones()
+
+    def check_hessian_ones(self):
+        """A zero-padded blur of a constant image is not constant, so the null-space argument of
+        `GMMPatchPrior.hessian_ones` does not hold across the levels, and there is no kernel for the product."""
+        raise NotImplementedError("compute_error=True is not implemented for a MultiScalePrior: the Hessian product with "
+                                  "ones is not zero behind a zero-padded blur")
+
+    def to_dict(self):
+        """The reference's keys (priors/patches/core.py:328-337)."""
+        return dict(
+            n_levels=self.n_levels,
+            weights=self.weights.detach().numpy().tolist(),
+            cycle_spin=self.cycle_spin,
+            anti_alias=self.anti_alias,
+            prior=self.prior.to_dict(),
+        )

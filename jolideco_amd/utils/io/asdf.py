@@ -35,6 +35,19 @@ def refuse_sparse(components, what):
             )
 
 
+def refuse_multiscale(components, what):
+    """No file layout has a slot for a `MultiScalePrior` (a prior around a prior, with a list of level weights), and the
+    reference cannot read one back either: writing a component that carries it is refused by name."""
+    members = components.items() if hasattr(components, "items") else [("component", components)]
+    for name, component in members:
+        prior = getattr(component, "prior", None)
+        if getattr(prior, "shift_kind", None) == "levels":
+            raise NotImplementedError(
+                f"{what} cannot carry the {type(prior).__name__} of the flux component {name!r}: the file layouts have no "
+                "slot for a multi-scale prior"
+            )
+
+
 def _write(tree, filename, overwrite):
     path = Path(filename)
     if path.exists() and not overwrite:
@@ -46,6 +59,7 @@ def _write(tree, filename, overwrite):
 def write_flux_component_to_asdf(flux_component, filename, overwrite, **kwargs):
     """Flux component(s) -> ASDF: the tree is ``to_dict(include_data="numpy")`` (reference: asdf.py:9-39)."""
     refuse_sparse(flux_component, "the ASDF format")
+    refuse_multiscale(flux_component, "the ASDF format")
     _write(flux_component.to_dict(include_data="numpy"), filename, overwrite)
 
 
@@ -72,6 +86,7 @@ def write_map_result_to_asdf(result, filename, overwrite, **kwargs):
     """`MAPDeconvolverResult` -> ASDF (reference: asdf.py:112-142): components, initial components, the loss trace as a
     table, the configuration."""
     refuse_sparse(result.components, "an ASDF result or checkpoint")
+    refuse_multiscale(result.components, "an ASDF result or checkpoint")
     tree = {"components": result.components.to_dict(include_data="numpy")}
     if result.components_init is not None:
         tree["components-init"] = result.components_init.to_dict(include_data="numpy")

@@ -76,6 +76,9 @@ def wcs_from_header(header):
 
 def flux_component_to_image_hdu(flux_component, name):
     """Flux component -> image HDU (reference: fits.py:115-143)."""
+    from .asdf import refuse_multiscale
+
+    refuse_multiscale({name: flux_component}, "the FITS format")
     header = Header()
     for key, value in (flux_component.wcs or {}).items():
         header[key] = value
@@ -103,6 +106,9 @@ def flux_component_from_image_hdu(hdu):
 
 def sparse_flux_component_to_table_hdu(flux_component, name):
     """Sparse flux component -> table HDU (reference: fits.py:43-84)."""
+    from .asdf import refuse_multiscale
+
+    refuse_multiscale({name: flux_component}, "the FITS format")
     header = Header()
     for key, value in (flux_component.wcs or {}).items():
         header[key] = value

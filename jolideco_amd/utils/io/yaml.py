@@ -50,9 +50,10 @@ def load_yaml(filename):
 
 def flux_component_to_yaml_dict(flux_component, filename, name=None):
     """Settings + the path of the companion data file (reference: yaml.py:97-119)."""
-    from .asdf import refuse_sparse
+    from .asdf import refuse_multiscale, refuse_sparse
 
     refuse_sparse({name or "component": flux_component}, "the YAML format")
+    refuse_multiscale({name or "component": flux_component}, "the YAML format")
     path = Path(filename)
     data = flux_component.to_dict()
     data["upsampling_factor"] = int(data["upsampling_factor"] or 1)
