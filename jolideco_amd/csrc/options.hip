@@ -40,6 +40,9 @@ OptionSlot g_options[OPT_COUNT] = {
     {"JD_GMM_GATHER_PRELOAD", {INT_MIN}},  // 0: the gather kernel loads the optimizer step's streams behind its block barrier
     {"JD_SEP_ADJ_ADDENDS", {INT_MIN}},  // 0: a joint step over both PSF frames adds every adjoint into the gradient image
                                         // (jd_npred_poisson_batch_addends_fwd_bwd writes no addend image)
+    {"JD_SEP_WALK_CHAIN", {INT_MIN}},  // waves per block of the plain strip walk (1-4): vertically adjacent tiles whose waves
+                                       // hand their first row-pass rows to the tile above; 1: one wave per block, no hand-over
+    {"JD_SEP_WALK_ADJ_CHAIN", {INT_MIN}},  // tuning: the same for plain adjoint walks and the addend launch alone
 };
 
 int parse(const char* text) {

@@ -15,7 +15,11 @@
 //     scale + accumulate for the adjoint).  At C = 4 the column pass runs on packed FMAs (two columns per instruction).
 // No second LDS image, no block barriers, no halo rows recomputed inside a tile: 34 FMAs, 1 + (16 + C) / C LDS floats
 // and one set of streaming loads per pixel; the only overhead is the 16 warm-up rows of a tile (R = 74: 22 % more row
-// passes).  Loads of row r + P are issued P steps ahead (registers), row taps live in SGPRs.  The launches follow their
+// passes).  In the CHAINED form of the plain walk (walk_chain_kernel, walk_mixed_chain_kernel: blocks of up to four waves
+// on vertically adjacent tiles; option JD_SEP_WALK_CHAIN) a wave takes the row-pass results of its last 16 rows from the
+// LDS stash of the wave below it, which computes them anyway as its first 16: the warm-up rows then cost their loads and
+// their column pass only.  It is the default where it was measured faster: the batched forward launch over both frames.
+// Loads of row r + P are issued P steps ahead (registers), row taps live in SGPRs.  The launches follow their
 // own instruction stream, not the memory system.
 //
 // Batched adjoint (the gradient of a joint step, sum over the datasets of E_d x corr(g_d, psf_d)): a block is one wave
@@ -23,6 +27,7 @@
 // add them in dataset order -- the additions of the per-dataset launches, bit for bit -- into the gradient image, which
 // is read and written once.  Several flux components: walk_multi_kernel (forward, one wave per component) and the same
 // adjoint over a grid of components x tiles with up to 16 waves per block.
+#include <algorithm>
 #include <cmath>
 #include <utility>
 
@@ -105,6 +110,7 @@ struct WalkArgs {
   int fin_count, fin_n;
   int* guard;                  // host-mapped: set when an operator is not rank 1
   int comp_blocks;             // batched adjoint over ALL components: blocks per component (0: component `comp` only)
+  int chain;                   // chained plain walk: waves (= vertically adjacent tiles of one strip) per block, 2-4
   float* out_comp[4];          //   and their gradient images
 };
 
@@ -163,24 +169,38 @@ __device__ __forceinline__ v2f pk_mul_stap(v2f taps, v2f h) {
 // w < XG adds up row w of a group); with a.comp_blocks > 0 the grid covers all flux components, comp_blocks blocks each.
 // `bid`: the block's index within the blocks of its frame; (strips, tiles_y, rows): their tiling; `slot0`: position of
 // the frame's first dataset in table->order (batched forward launches).
-template <int WKT, int C, int P, bool POISSON, bool IN_SCALE, int XG, int XWT>
+// CH: the CHAINED plain walk (XG == 0 only).  A block is a.chain waves that own vertically adjacent tiles of one strip of
+// one dataset.  The first 2 WH rows a tile walks are the last 2 WH rows of the tile above it: every wave but the first
+// of its chain stashes the row-pass results h of those rows in LDS as it computes them (2 WH rows of 64 C floats), one
+// block barrier sits behind the first round of WS steps (WS > 2 WH: the stash is complete there; the host only chains
+// tiles of k WS - 2 WH rows, k >= 2: their last 2 WH steps are the steps WS - 2 WH .. WS - 1 of a LATER round -- static
+// places of the unrolled loop, chosen by one scalar flag per round), and a wave with a lower neighbour takes h of its last
+// 2 WH rows from that neighbour's stash -- one LDS read per row instead of product, exchange and row pass.  The value is
+// the one the wave would have computed (same loads, masks and arithmetic): the results are the same bits.  The streaming
+// loads of the handed-over rows stay (every step issues the same loads: the compiler goes on counting them exactly).
+template <int WKT, int C, int P, bool POISSON, bool IN_SCALE, int XG, int XWT, bool CH = false>
 __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int strips, const int tiles_y, const int rows,
                                           const int slot0) {
 #pragma clang fp contract(off)  // every fused multiply-add below is an explicit fmaf: batched and per-dataset paths round alike
   constexpr int WK = Frame<WKT>::WK, WH = Frame<WKT>::WH, WS = Frame<WKT>::WS;
   constexpr bool XCHG = XG > 0;
   static_assert(!XCHG || (WS % XG == 0 && XG <= XG_MAX), "the exchange group must divide the rotation period");
+  static_assert(!(CH && XCHG) && !(CH && JD_WALK_PKROW), "the chained walk is the plain walk with the scalar row pass");
+  static_assert(WS > 2 * WH, "the stash must be complete behind the first round");
   typedef typename Vec<C>::T vC;
   constexpr int NX = 2 * WH / C;       // lanes that also load the right-hand halo piece
   constexpr int NWIN = 2 * WH + C;     // window floats per lane
   static_assert(64 * C + C * 64 <= 2 * 64 * C && NX <= 64, "row buffer");
   __shared__ __attribute__((aligned(16))) float rowbuf[XCHG ? XWT : 1][2 * 64 * C];  // 64 C + 2 WH floats used, the rest is a dump
   __shared__ __attribute__((aligned(16))) float xbuf[XCHG ? 2 * XG * XWT * 64 * C : 4];
+  // CH (dynamic, sized by the host): a.chain row buffers, then the stashes of the waves 1 .. a.chain - 1
+  extern __shared__ __attribute__((aligned(16))) float chain_lds[];
   vC oprev;  // XCHG: the row of the gradient image this wave adds a group's row to, requested at the group's start
   __shared__ double fin_red[4];
 
   const int lane = threadIdx.x & 63;
-  const int wv = XCHG ? (int)(threadIdx.x >> 6) : 0;
+  // (CH: scalar, so that everything derived from the wave's tile stays in SGPRs as it does with one wave per block)
+  const int wv = XCHG ? (int)(threadIdx.x >> 6) : CH ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
   const int nb = XCHG ? (int)(blockDim.x >> 6) : 1;
 
   if (XCHG && a.fin_partials && (int)blockIdx.x < a.fin_n) {  // (block-uniform; the host asks only with >= 256 threads)
@@ -202,8 +222,12 @@ __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int 
   }
 
   // consecutive tiles of one XCD (blockIdx % 8) are vertical neighbours in a strip: their halo rows hit in that L2
+  // (CH: the same order in units of chains, chain k of a strip being its tiles k L .. k L + L - 1)
   const int n_tiles = strips * tiles_y;
-  const int per_xcd = (n_tiles + 7) / 8;
+  const int L = CH ? a.chain : 1;
+  const int chains_y = CH ? (tiles_y + L - 1) / L : tiles_y;
+  const int n_units = CH ? strips * chains_y : n_tiles;
+  const int per_xcd = (n_units + 7) / 8;
   int comp = a.comp;
   if (XCHG && a.comp_blocks) comp = bid / a.comp_blocks, bid -= comp * a.comp_blocks;  // (comp_blocks: a multiple of 8)
   const int q = bid / 8;
@@ -212,9 +236,16 @@ __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int 
   // share within a row or two of each other)
   const int ilv = !XCHG && a.n_batch > 0 ? (slot0 ? a.ilv33 : a.ilv17) : 0;
   const int dsel = (!XCHG && a.n_batch > 0) ? a.table->order[slot0 + (ilv ? q % ilv : q / per_xcd)] : 0;
-  const int tile = (bid % 8) * per_xcd + (ilv ? q / ilv : q % per_xcd);
-  if (tile >= n_tiles) return;  // (block-uniform)
-  const int sx = tile / tiles_y, ty = tile - sx * tiles_y;
+  const int unit = (bid % 8) * per_xcd + (ilv ? q / ilv : q % per_xcd);
+  if (unit >= n_units) return;  // (block-uniform)
+  const int sx = unit / chains_y, ty = CH ? (unit - sx * chains_y) * L + wv : unit - sx * tiles_y;
+  const int tile = CH ? sx * tiles_y + ty : unit;
+  if constexpr (CH) {
+    if (ty >= tiles_y) {  // (wave-uniform) a chain that ends at the image's last tile: no wave leaves before the barrier
+      __syncthreads();
+      return;
+    }
+  }
 
   // (global address space stated: pointers that come out of the table are generic to the compiler, and generic loads are
   // `flat_` instructions, which complete out of order and force a full s_waitcnt at every step)
@@ -281,7 +312,15 @@ __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int 
   const unsigned om = vm ? xm : 0, oe = ve ? xe : (xd < a.W ? xd : 0), oo = vo ? xo : 0;
   const int Y0 = ty * rows, y_end = min(Y0 + rows, a.H);
   const int r_begin = Y0 - WH, r_end = min(y_end + WH, a.H);  // image rows >= H contribute nothing
-  float* rb = rowbuf[wv];
+  float* rb = CH ? chain_lds + wv * (2 * 64 * C) : rowbuf[wv];
+  // CH: this wave's stash (waves > 0) and the one of its lower neighbour, whose first walked row is image row hand0
+  constexpr int SROWS = 2 * WH;
+  float* const stash_w = chain_lds + L * (2 * 64 * C) + (wv - 1) * (SROWS * 64 * C) + C * lane;
+  const float* const stash_r = chain_lds + L * (2 * 64 * C) + wv * (SROWS * 64 * C) + C * lane;
+  const bool stash_on = CH && wv > 0, has_next = CH && wv + 1 < L && ty + 1 < tiles_y;
+  const int hand0 = Y0 + rows - WH;
+  constexpr int HAND_I = WS - SROWS;  // rotation state of the first handed-over step (tiles of k WS - 2 WH rows)
+  bool hand_now = false, stash_now = false;  // (wave-uniform, set per round) this round ends on the handed-over rows / stashes
 
   struct Row { vC a, s, xa, xs; };
   struct Epi { vC p, q; };  // POISSON: background, counts; plain: out_scale, previous out
@@ -388,33 +427,47 @@ __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int 
   float W[2][NWIN];
   // (rows outside the image go through the exchange too -- clamped loads, never used: every step issues the same LDS
   // operations, so the compiler counts the ones in flight exactly instead of waiting for all of them at a join)
-  auto produce = [&](int rr1, Row& nx, float (&w)[NWIN]) {
-    // ---- products of the row -> LDS ----------------------------------------------------------------------------
-    vC prod = nx.a;
-    if (IN_SCALE) prod = prod * nx.s;
+  // (handed -- CH only: the neighbour's h of this row, row j of its stash, arrives in w[0 .. C) in place of the window)
+  auto produce = [&](int rr1, Row& nx, float (&w)[NWIN], const bool handed, const int j) {
+    if (!handed) {
+      // ---- products of the row -> LDS --------------------------------------------------------------------------
+      vC prod = nx.a;
+      if (IN_SCALE) prod = prod * nx.s;
 #pragma unroll
-    for (int c = 0; c < C; ++c) prod[c] = vm ? prod[c] : 0.f;
-    *reinterpret_cast<vC*>(rb + C * lane) = prod;
-    vC px = nx.xa;
-    if (IN_SCALE) px = px * nx.xs;
+      for (int c = 0; c < C; ++c) prod[c] = vm ? prod[c] : 0.f;
+      *reinterpret_cast<vC*>(rb + C * lane) = prod;
+      vC px = nx.xa;
+      if (IN_SCALE) px = px * nx.xs;
 #pragma unroll
-    for (int c = 0; c < C; ++c) px[c] = ve ? px[c] : 0.f;
-    *reinterpret_cast<vC*>(rb + 64 * C + C * lane) = px;  // (lanes >= NX: behind the window, never read)
-    load_row(rr1 + P, nx);  // the row P steps ahead takes this row's registers
-    wave_lds_fence();
-#pragma unroll
-    for (int k = 0; k < NWIN / C; ++k) {
-      const vC t = *reinterpret_cast<const vC*>(rb + C * lane + C * k);
-#pragma unroll
-      for (int c = 0; c < C; ++c) w[C * k + c] = t[c];
+      for (int c = 0; c < C; ++c) px[c] = ve ? px[c] : 0.f;
+      *reinterpret_cast<vC*>(rb + 64 * C + C * lane) = px;  // (lanes >= NX: behind the window, never read)
     }
-    wave_lds_fence();
+    load_row(rr1 + P, nx);  // the row P steps ahead takes this row's registers
+    if (!handed) {
+      wave_lds_fence();
+#pragma unroll
+      for (int k = 0; k < NWIN / C; ++k) {
+        const vC t = *reinterpret_cast<const vC*>(rb + C * lane + C * k);
+#pragma unroll
+        for (int c = 0; c < C; ++c) w[C * k + c] = t[c];
+      }
+      wave_lds_fence();
+    } else {
+      const vC t = *reinterpret_cast<const vC*>(stash_r + j * (64 * C));
+#pragma unroll
+      for (int c = 0; c < C; ++c) w[c] = t[c];
+      // (the rest of the window holds nothing on this path; said with an empty asm, or the compiler carries the values
+      // of two steps ago through the branch and copies all of them at every join)
+#pragma unroll
+      for (int k = C; k < NWIN; ++k) asm volatile("" : "=v"(w[k]));
+    }
   };
-  produce(r_begin, pf[0], W[0]);
+  produce(r_begin, pf[0], W[0], false, 0);
 
 #endif
 
   for (int r0 = r_begin; r0 < y_end + WH + (XCHG ? XG - 1 : 0); r0 += WS) {  // (+: the last group's flush step)
+    if constexpr (CH) hand_now = has_next && r0 + HAND_I == hand0, stash_now = stash_on && r0 == r_begin;
     static_for<WS>([&](auto ic) {  // (the 18 rotation states as compile-time constants: see walk_multi_kernel)
       constexpr int i = decltype(ic)::value;
       const int rr = r0 + i;
@@ -446,17 +499,30 @@ __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int 
 #pragma unroll
         for (int c = 0; c < C; ++c) h[c] = hp[c / 2][c % 2];
 #else
-      produce(rr + 1, pf[(i + 1) % P], W[(i + 1) & 1]);
+      produce(rr + 1, pf[(i + 1) % P], W[(i + 1) & 1], CH && i + 1 >= HAND_I && i + 1 < WS && hand_now, i + 1 - HAND_I);
       if (live) {
         const float (&w)[NWIN] = W[i & 1];
         // ---- row pass: h[c] = sum_t tv[t] w[c + t] -----------------------------------------------------------
         float h[C];
+        if (CH && i >= HAND_I && hand_now) {
 #pragma unroll
-        for (int c = 0; c < C; ++c) h[c] = tv[0] * w[c];
+          for (int c = 0; c < C; ++c) h[c] = w[c];
+        } else {
 #pragma unroll
-        for (int t = 1; t < WK; ++t)
+          for (int c = 0; c < C; ++c) h[c] = tv[0] * w[c];
 #pragma unroll
-          for (int c = 0; c < C; ++c) h[c] = fmaf(tv[t], w[c + t], h[c]);
+          for (int t = 1; t < WK; ++t)
+#pragma unroll
+            for (int c = 0; c < C; ++c) h[c] = fmaf(tv[t], w[c + t], h[c]);
+        }
+        if constexpr (CH && i < SROWS) {
+          if (stash_now) {  // (wave-uniform) the tile's first 2 WH rows: the tile above ends on them
+            vC hv;
+#pragma unroll
+            for (int c = 0; c < C; ++c) hv[c] = h[c];
+            *reinterpret_cast<vC*>(stash_w + i * (64 * C)) = hv;
+          }
+        }
         v2f hp[C / 2];
 #pragma unroll
         for (int c = 0; c < C; ++c) hp[c / 2][c % 2] = h[c];
@@ -543,6 +609,9 @@ __device__ __forceinline__ void walk_body(const WalkArgs& a, int bid, const int 
       }
       load_epi(y + P, ce);
     });
+    if constexpr (CH) {
+      if (r0 == r_begin) __syncthreads();  // every stash of the block is complete; the first hand-over comes later
+    }
   }
   if (POISSON) {
     loss = wave_sum(loss);
@@ -562,6 +631,13 @@ __global__ __launch_bounds__(XG ? 64 * XWT : 64) void walk_kernel(WalkArgs a) {
   walk_body<WKT, C, P, POISSON, IN_SCALE, XG, XWT>(a, (int)blockIdx.x, a.strips, a.tiles_y, a.rows, POISSON ? 0 : a.order0);
 }
 
+// The chained plain walk: blocks of a.chain <= 4 waves; two waves per SIMD, whatever the block size
+constexpr int CHAIN_MAX = 4;
+template <int WKT, int C, int P, bool POISSON, bool IN_SCALE>
+__global__ __launch_bounds__(64 * CHAIN_MAX, 2) void walk_chain_kernel(WalkArgs a) {
+  walk_body<WKT, C, P, POISSON, IN_SCALE, 0, XW, true>(a, (int)blockIdx.x, a.strips, a.tiles_y, a.rows, POISSON ? 0 : a.order0);
+}
+
 // Batched forward launch over operators of both frames: the 17-tap datasets at C17 columns per lane, the 33-tap
 // datasets behind them at two (every wave of the launch resident at once; the host sizes the two tilings so that the
 // waves of both kinds take about as long).
@@ -571,6 +647,14 @@ __global__ __launch_bounds__(64) void walk_mixed_kernel(WalkArgs a) {
     walk_body<17, C17, P, true, true, 0, XW>(a, (int)blockIdx.x, a.strips, a.tiles_y, a.rows, 0);
   else
     walk_body<33, 2, P, true, true, 0, XW>(a, (int)blockIdx.x - a.blocks17, a.strips33, a.tiles_y33, a.rows33, a.n17);
+}
+
+template <int C17, int P>
+__global__ __launch_bounds__(64 * CHAIN_MAX, 2) void walk_mixed_chain_kernel(WalkArgs a) {
+  if ((int)blockIdx.x < a.blocks17)  // (block-uniform)
+    walk_body<17, C17, P, true, true, 0, XW, true>(a, (int)blockIdx.x, a.strips, a.tiles_y, a.rows, 0);
+  else
+    walk_body<33, 2, P, true, true, 0, XW, true>(a, (int)blockIdx.x - a.blocks17, a.strips33, a.tiles_y33, a.rows33, a.n17);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1223,19 +1307,61 @@ void walk_shape(const WalkArgs& a, int n, bool adjoint, int frame, int* C, int* 
   if (orows >= 20 && orows <= 4096) *rows = orows;
 }
 
+// Chain length of a plain walk launch on tiles of `rows` rows: option JD_SEP_WALK_CHAIN (1-4; JD_SEP_WALK_ADJ_CHAIN, where
+// set, for plain adjoints and the addend launch), else the launch's own default;
+// 1 unless the tiles are k WS - 2 WH rows tall, k >= 2 (the heights walk_shape chooses: the hand-over then falls on the
+// last 2 WH steps of a round behind the block barrier).
+// Defaults, measured inside the fit on MI355X (tools/ab.py, profiles/walk_chain/README.md): the batched forward launch over
+// both frames (2048^2, 6 + 2 datasets) 126.7 -> 119.5 us at chains of 4 (2: 130.6, 3: 155.5 -- three-wave blocks do not
+// fill the eight wave slots of a CU); the addend launch, which runs beside the GMM screen kernel, +11 us per step at chains
+// of 4 and no gain at 2 (a block needs its wave slots and up to 56 KB of LDS on ONE CU at once); forward launch and adjoint of one
+// 4096^2 dataset (memory bound) 91.7 -> 93.0 and 46.9 -> 50.7 us.  A batched launch of one frame is unmeasured.
+// The mixed launch takes its chains only where all of its blocks are resident at once (walk_conv_poisson_batch).
+constexpr int CHAIN_DEFAULT = 1, CHAIN_MIXED = 4;
+int walk_chain(int dflt, int frame, int rows, bool adjoint = false) {
+  int L = opt_value(OPT_SEP_WALK_CHAIN, dflt);
+  if (adjoint) L = opt_value(OPT_SEP_WALK_ADJ_CHAIN, L);  // (tuning: the adjoint-side launches apart from the forward ones)
+  L = L < 1 ? 1 : L > CHAIN_MAX ? CHAIN_MAX : L;
+  const int ws = frame == 33 ? Frame<33>::WS : Frame<17>::WS, wh = frame == 33 ? Frame<33>::WH : Frame<17>::WH;
+  return (rows + 2 * wh) % ws == 0 && rows + 2 * wh >= 2 * ws ? L : 1;
+}
+// LDS of a chained block: L row buffers and L - 1 stashes of 2 WH rows (56 KB at L = 4 in both frames' widest form)
+size_t chain_lds_bytes(int L, int frame, int C) {
+  const int wh = frame == 33 ? Frame<33>::WH : Frame<17>::WH;
+  return (size_t)(L * 2 * 64 * C + (L - 1) * 2 * wh * 64 * C) * sizeof(float);
+}
+// blocks per dataset of a tiling in chains of L: a multiple of 8 (the XCD-aware order)
+int walk_blocks(int strips, int tiles_y, int L) { return (strips * ((tiles_y + L - 1) / L) + 7) / 8 * 8; }
+
+// the plain walk of a.chain-wave blocks over n_grid datasets (no guard check, no profile scope: the callers')
+template <bool POISSON, bool IN_SCALE>
+void launch_plain(const WalkArgs& a, int frame, int C, int n_grid, hipStream_t stream) {
+  const int L = a.chain > 1 ? a.chain : 1;
+  const unsigned blocks = (unsigned)(walk_blocks(a.strips, a.tiles_y, L) * n_grid);
+  if (L == 1) {
+    if (frame == 33)
+      hipLaunchKernelGGL((walk_kernel<33, 2, WALK_PREFETCH, POISSON, IN_SCALE, 0>), dim3(blocks), dim3(64), 0, stream, a);
+    else if (C == 4)
+      hipLaunchKernelGGL((walk_kernel<17, 4, WALK_PREFETCH, POISSON, IN_SCALE, 0>), dim3(blocks), dim3(64), 0, stream, a);
+    else
+      hipLaunchKernelGGL((walk_kernel<17, 2, WALK_PREFETCH, POISSON, IN_SCALE, 0>), dim3(blocks), dim3(64), 0, stream, a);
+    return;
+  }
+  const size_t lds = chain_lds_bytes(L, frame, frame == 33 ? 2 : C);
+  if (frame == 33)
+    hipLaunchKernelGGL((walk_chain_kernel<33, 2, WALK_PREFETCH, POISSON, IN_SCALE>), dim3(blocks), dim3(64 * L), lds, stream, a);
+  else if (C == 4)
+    hipLaunchKernelGGL((walk_chain_kernel<17, 4, WALK_PREFETCH, POISSON, IN_SCALE>), dim3(blocks), dim3(64 * L), lds, stream, a);
+  else
+    hipLaunchKernelGGL((walk_chain_kernel<17, 2, WALK_PREFETCH, POISSON, IN_SCALE>), dim3(blocks), dim3(64 * L), lds, stream, a);
+}
+
 template <bool POISSON, bool IN_SCALE>
 int launch_walk(WalkArgs a, int frame, int C, int n_grid, hipStream_t stream) {
   int rc = sep_guard_check(&a.guard);
   if (rc) return rc;
-  const int n_tiles = a.strips * a.tiles_y;
-  const unsigned blocks = (unsigned)(((n_tiles + 7) / 8) * 8 * n_grid);
   ProfScope prof(POISSON ? JD_KERNEL_POISSON_FUSED : JD_KERNEL_SEP_CONV, stream);
-  if (frame == 33)
-    hipLaunchKernelGGL((walk_kernel<33, 2, WALK_PREFETCH, POISSON, IN_SCALE, 0>), dim3(blocks), dim3(64), 0, stream, a);
-  else if (C == 4)
-    hipLaunchKernelGGL((walk_kernel<17, 4, WALK_PREFETCH, POISSON, IN_SCALE, 0>), dim3(blocks), dim3(64), 0, stream, a);
-  else
-    hipLaunchKernelGGL((walk_kernel<17, 2, WALK_PREFETCH, POISSON, IN_SCALE, 0>), dim3(blocks), dim3(64), 0, stream, a);
+  launch_plain<POISSON, IN_SCALE>(a, frame, C, n_grid, stream);
   JD_LAUNCH_CHECK();
   return JD_OK;
 }
@@ -1316,6 +1442,7 @@ int walk_conv(const float* in, const float* in_scale, const float* op, float* ou
   int C, rows;
   walk_shape(a, 1, adjoint != 0, frame, &C, &rows);
   walk_tiles(a, C, rows);
+  a.chain = walk_chain(CHAIN_DEFAULT, frame, rows, adjoint != 0);
   return in_scale ? launch_walk<false, true>(a, frame, C, 1, stream) : launch_walk<false, false>(a, frame, C, 1, stream);
 }
 
@@ -1338,6 +1465,7 @@ int walk_conv_poisson(const float* in, const float* in_scale, const float* op, f
   int C, rows;
   walk_shape(a, 1, false, frame, &C, &rows);
   walk_tiles(a, C, rows);
+  a.chain = walk_chain(CHAIN_DEFAULT, frame, rows);
   *n_partials = a.strips * a.tiles_y;
   return launch_walk<true, true>(a, frame, C, 1, stream);
 }
@@ -1365,6 +1493,7 @@ int walk_conv_poisson_batch(int n, const float* flux, const SepBatchTable& table
     const int frame = n33 ? 33 : 17;
     walk_shape(a, n, false, frame, &C, &rows);
     walk_tiles(a, C, rows);
+    a.chain = walk_chain(CHAIN_DEFAULT, frame, rows);
     *n_partials = a.strips * a.tiles_y;
     if (opt_is_set(OPT_SEP_INTERLEAVE)) a.ilv17 = n;
     return launch_walk<true, true>(a, frame, C, n, stream);
@@ -1401,14 +1530,35 @@ int walk_conv_poisson_batch(int n, const float* flux, const SepBatchTable& table
   const int t17 = a.strips * a.tiles_y, t33 = a.strips33 * a.tiles_y33;
   a.n17 = n17;
   if (opt_is_set(OPT_SEP_INTERLEAVE)) a.ilv17 = n17, a.ilv33 = n33;
-  a.blocks17 = ((t17 + 7) / 8) * 8 * n17;
+  // (one block size per launch: both frames' tiles chained alike, or -- a tiling of either no taller than a round -- not at all)
+  int L = std::min(walk_chain(CHAIN_MIXED, 17, rows), walk_chain(CHAIN_MIXED, 33, rows33));
+  // Every block of the launch must be resident at once, as every wave is with one wave per block: the tilings above are
+  // sized in single waves, but a chain is rounded up to whole blocks (per strip, and to 8 blocks per dataset), and a CU
+  // holds only as many blocks of L waves as its 8 wave slots and its 160 KB of LDS allow -- two at L = 4.  A launch with
+  // more blocks than that runs a second round of them (measured with three-wave blocks, which do not fill the slots
+  // either: 155.5 against 126.7 us), so the DEFAULT chain length is taken only where the blocks fit, else 1 (chains of 2
+  // and 3 were measured slower than single waves where they do fit).  An option set by hand is taken as it is.
+  if (L > 1 && !opt_is_set(OPT_SEP_WALK_CHAIN)) {
+    const size_t lds = std::max(chain_lds_bytes(L, 17, C), chain_lds_bytes(L, 33, 2));
+    const long per_cu = std::min<long>(8 / L, (long)(160 * 1024 / lds));
+    const long blocks = (long)walk_blocks(a.strips, a.tiles_y, L) * n17 + (long)walk_blocks(a.strips33, a.tiles_y33, L) * n33;
+    if (blocks > per_cu * device_cus()) L = 1;
+  }
+  a.chain = L;
+  a.blocks17 = walk_blocks(a.strips, a.tiles_y, L) * n17;
   a.part_stride = t17 > t33 ? t17 : t33;
   *n_partials = a.part_stride;
   int rc = sep_guard_check(&a.guard);
   if (rc) return rc;
-  const unsigned blocks = (unsigned)(a.blocks17 + ((t33 + 7) / 8) * 8 * n33);
+  const unsigned blocks = (unsigned)(a.blocks17 + walk_blocks(a.strips33, a.tiles_y33, L) * n33);
   ProfScope prof(JD_KERNEL_POISSON_FUSED, stream);
-  if (C == 4)
+  if (L > 1) {
+    const size_t lds = std::max(chain_lds_bytes(L, 17, C), chain_lds_bytes(L, 33, 2));
+    if (C == 4)
+      hipLaunchKernelGGL((walk_mixed_chain_kernel<4, WALK_PREFETCH>), dim3(blocks), dim3(64 * L), lds, stream, a);
+    else
+      hipLaunchKernelGGL((walk_mixed_chain_kernel<2, WALK_PREFETCH>), dim3(blocks), dim3(64 * L), lds, stream, a);
+  } else if (C == 4)
     hipLaunchKernelGGL((walk_mixed_kernel<4, WALK_PREFETCH>), dim3(blocks), dim3(64), 0, stream, a);
   else
     hipLaunchKernelGGL((walk_mixed_kernel<2, WALK_PREFETCH>), dim3(blocks), dim3(64), 0, stream, a);
@@ -1559,6 +1709,7 @@ int walk_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTable& ta
     const int orows1 = opt_value(frame == 33 ? OPT_SEP_WALK_ADJ_ROWS33 : OPT_SEP_WALK_ADJ_ROWS, 0);
     if (orows1 >= 20 && orows1 <= 4096) r1 = orows1;  // (tuning: the adjoint tile height option of the launch's frame)
     walk_tiles(b, C1, r1);
+    b.chain = walk_chain(CHAIN_DEFAULT, frame, r1, true);
     if (beside) {
       JD_HIP(hipEventRecord(fork_join[0], stream));
       JD_HIP(hipStreamWaitEvent(stream2, fork_join[0], 0));
@@ -1638,13 +1789,8 @@ int walk_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTable& ta
       walk_shape(b, 1, true, frame, &C1, &r1);
       if (frame == 33 && orows >= 18) r1 = orows;
       walk_tiles(b, C1, r1);
-      const unsigned blocks1 = (unsigned)(((b.strips * b.tiles_y + 7) / 8) * 8);
-      if (frame == 33)
-        hipLaunchKernelGGL((walk_kernel<33, 2, WALK_PREFETCH, false, false, 0>), dim3(blocks1), dim3(64), 0, stream, b);
-      else if (C1 == 4)
-        hipLaunchKernelGGL((walk_kernel<17, 4, WALK_PREFETCH, false, false, 0>), dim3(blocks1), dim3(64), 0, stream, b);
-      else
-        hipLaunchKernelGGL((walk_kernel<17, 2, WALK_PREFETCH, false, false, 0>), dim3(blocks1), dim3(64), 0, stream, b);
+      b.chain = walk_chain(CHAIN_DEFAULT, frame, r1, true);
+      launch_plain<false, false>(b, frame, C1, 1, stream);
     }
     JD_LAUNCH_CHECK();
     d0 += m;
