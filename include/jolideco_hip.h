@@ -466,7 +466,8 @@ int jd_add_rolled_bands(float* grad, int H, int W, int shift_y, int shift_x, con
  * last term of the gradient): every pixel takes g = step->grad_flux[pixel] + (the band sum above, same additions in the
  * same order) -- the gradient image itself is only read -- and the update of jd_adam_step with g: the bits of
  * jd_add_rolled_bands followed by jd_adam_step, one launch and one pass over the gradient image less.  Needs W % 4 == 0
- * and 16-byte aligned images (JD_ERR_INVALID otherwise: use the two calls). */
+ * and 16-byte aligned images (JD_ERR_INVALID otherwise: use the two calls).  step->addend is not supported here: a
+ * non-null step->addend[0] returns JD_ERR_INVALID (use jd_add_rolled_bands + jd_adam_step_addends). */
 int jd_add_rolled_bands_step(int H, int W, int shift_y, int shift_x, const float* bands, size_t chunk_floats, int n_bands,
                              const int* y_begin, const int* y_end, const jd_step* step, void* stream);
 
@@ -551,7 +552,7 @@ int jd_adam_step_multi(int n_tensors, float* const* theta, const float* const* g
                        float* const* exp_avg_sq, const int* sizes, const float* step_size, const float* bias2_sqrt,
                        float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
                        const float* bias_dev, void* stream);
-/* plain SGD (core.py:41): theta -= lr * grad_flux * flux_in */
+/* plain SGD (core.py:41): theta -= lr * grad_flux * flux_in, the update as ONE fused multiply-add (torch's add_(grad, alpha=-lr)) */
 int jd_sgd_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
                 const float* mask, size_t n, float lr, int zero_grad, int use_log_flux, void* stream);
 

@@ -710,8 +710,11 @@ static void launch_adam_kernel(bool vec, unsigned blocks, const AdamArgs& a, hip
 static int launch_adam(const AdamArgs& a, hipStream_t stream) {
   int na = 0;
   while (na < ADDEND_MAX && a.addend[na]) ++na;
-  bool vec = (a.n % 4 == 0);
-  for (int k = 0; k < na; ++k) vec = vec && (reinterpret_cast<uintptr_t>(a.addend[k]) & 15) == 0;
+  // float4 accesses: every image the kernel touches is 16-byte aligned (null m, v, mask count as aligned), else pixel by pixel
+  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
+  bool vec = (a.n % 4 == 0) && aligned(a.theta) && aligned(a.flux_in) && aligned(a.flux_out) && aligned(a.grad_flux) &&
+             aligned(a.m) && aligned(a.v) && aligned(a.mask);
+  for (int k = 0; k < na; ++k) vec = vec && aligned(a.addend[k]);
   const size_t per_block = (size_t)BLOCK * (vec ? 4 : 1);
   size_t blocks = (a.n + per_block - 1) / per_block;
   if (blocks > 4096) blocks = 4096;

@@ -398,8 +398,8 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
   if (step) {
     ga.do_step = 1, ga.step = *step, ga.y_begin = 0, ga.y_end = H;  // every pixel of the image takes the step
     ga.preload = opt_value(OPT_GMM_GATHER_PRELOAD, 1) != 0;
-    ga.vec = ga.vec && aligned(step->theta) && aligned(step->flux_in) && aligned(step->flux_out) && aligned(step->m) &&
-             aligned(step->v) && aligned(step->mask);
+    ga.vec = ga.vec && aligned(step->theta) && aligned(step->flux_in) && aligned(step->flux_out) && aligned(step->grad_flux) &&
+             aligned(step->m) && aligned(step->v) && aligned(step->mask);
     for (int k = 0; k < ADDEND_MAX; ++k) ga.vec = ga.vec && aligned(step->addend[k]);
   }
   return launch_gather(ga, s);

@@ -493,6 +493,7 @@ extern "C" int jd_add_rolled_bands_step(int H, int W, int shift_y, int shift_x, 
   JD_REQUIRE(bands && y_begin && y_end && step, "jd_add_rolled_bands_step: null argument");
   JD_REQUIRE(step->theta && step->flux_in && step->flux_out && step->grad_flux, "jd_add_rolled_bands_step: null image");
   JD_REQUIRE(step->sgd || (step->exp_avg && step->exp_avg_sq), "jd_add_rolled_bands_step: Adam needs its moment images");
+  JD_REQUIRE(!step->addend[0], "jd_add_rolled_bands_step: addend images are not supported (use jd_add_rolled_bands + jd_adam_step_addends)");
   JD_REQUIRE(n_bands >= 1 && n_bands <= BANDS_MAX, "jd_add_rolled_bands_step: %d bands not in [1, %d]", n_bands, BANDS_MAX);
   auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
   JD_REQUIRE(W % 4 == 0 && aligned(step->theta) && aligned(step->flux_in) && aligned(step->flux_out) && aligned(step->grad_flux) &&

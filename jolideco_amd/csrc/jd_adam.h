@@ -39,7 +39,10 @@ __device__ inline void adam_update(float& th, float& m, float& v, float g, const
 #pragma clang fp contract(off)
 #endif
   if (a.sgd) {
-    th = th - a.lr * g;
+    // param.add_(grad, alpha=-lr) of torch.optim.SGD is ONE fused multiply-add (its float32 CPU kernel, bit for bit): the
+    // bits of torch, and where the update nearly cancels the parameter a quarter of the error of a product rounded on its
+    // own (tests/test_gpu_optimizer_step.py).  An explicit fmaf fuses in every kernel, whatever the contract pragma says.
+    th = fmaf(-a.lr, g, th);
     return;
   }
   // exp_avg.lerp_(grad, 1 - beta1); exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)

@@ -75,6 +75,15 @@ def test_argument_validation_reports_errors(lib):
     assert b"null argument" in lib.jd_last_error()
     total, count = ctypes.c_double(), ctypes.c_longlong()
     assert lib.jd_profile_read(99, ctypes.byref(total), ctypes.byref(count)) == -1
+    # the band sum's fused step takes no addend images (non-null dummy pointers: the call returns before it looks at them)
+    from jolideco_amd import _hip
+
+    dummy = ctypes.c_void_p(64)
+    step = _hip.Step(theta=64, flux_in=64, flux_out=64, grad_flux=64, sgd=1, use_log_flux=1)
+    step.addend[0] = 64
+    rows = (ctypes.c_int * 1)(0)
+    assert lib.jd_add_rolled_bands_step(8, 8, 0, 0, dummy, 64, 1, rows, rows, ctypes.byref(step), None) == -1
+    assert b"addend images are not supported" in lib.jd_last_error()
     # destroying a null handle is a no-op
     assert lib.jd_conv_plan_destroy(None) == 0 and lib.jd_gmm_destroy(None) == 0
 

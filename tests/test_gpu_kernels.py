@@ -241,7 +241,7 @@ def test_adam_step_matches_torch_optim():
     from jolideco_amd.ops import adam_bias_terms
 
     rs = np.random.RandomState(5)
-    n = 1000 * 4 + 3  # exercises the scalar tail path
+    n = 1000 * 4 + 3  # n % 4 != 0: the whole launch runs the scalar kernel (tests/test_gpu_optimizer_step.py: the float4 one)
     theta0 = rs.normal(size=n).astype(np.float32)
     ref_p = torch.nn.Parameter(torch.from_numpy(theta0.copy()))
     opt = torch.optim.Adam([ref_p], lr=0.1)
