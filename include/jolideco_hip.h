@@ -118,6 +118,17 @@ int jd_conv_plan_takes_walk(const jd_conv_plan* plan, int n_datasets);
  *             2 the FFT launches dataset by dataset and the tail over all
  *   [7]       transposed shift: R = 1, 2, 4 rows per thread of the four-pixel kernel (16-byte aligned images), 0 scalar kernels */
 int jd_conv_plan_step_route(const jd_conv_plan* plan, int upsampling, int n_datasets, int32_t* route8);
+/* Which instantiation of the MFMA Toeplitz kernel (csrc/directconv.hip) a DIRECT plan launches -- computed by the functions
+ * the launch itself calls, from the plan's own fields; read-only, no device work; an error for a plan of another method.
+ * kernel4 =
+ *   [0]  KC, the input columns of one Toeplitz product: fp32 kernel 16, 20, .. 48 (15 + kw rounded up to a multiple of 4),
+ *        split-fp16 kernel 32 (kw <= 17) or 64
+ *   [1]  1: the split-fp16 kernel, 0: the fp32 one (a PSF whose planes and table do not fit in LDS, or JD_DIRECT_FP32=1)
+ *   [2]  1 when the forward convolution stages its window in 16-byte chunks, given 16-byte aligned images (the shape part
+ *        of the condition: W % 4 == 0 and the window's first column a multiple of 4); 0: element by element
+ *   [3]  the same for the adjoint
+ * (The float4 epilogue has a condition of its own: W % 4 == 0 and every image it touches 16-byte aligned.) */
+int jd_conv_plan_direct_kernel(const jd_conv_plan* plan, int32_t* kernel4);
 /* The frame -- 17 or 33 taps per direction -- in which the strip-walk kernels run the operator `khat` that
  * jd_conv_psf_spectrum built for this SEPARABLE plan, or 0 when they do not take it (rank > 1, non-zero taps wider than 33,
  * a buffer the library did not build).  The frame follows from the NON-ZERO taps of the operator, not from the plan's

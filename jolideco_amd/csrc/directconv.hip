@@ -64,6 +64,8 @@ struct DirectConvArgs {
   double* partials;         // n_tiles
   float eps, inv_n;
   int write_grad;
+  // float4 epilogue: W % 4 == 0 and every image the epilogue touches 16-byte aligned (set by launch_kc)
+  int epi_vec;
 };
 
 // Persistent, software pipelined: a block walks over its tiles; while the MFMAs of tile i run out of
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(256) void direct_conv_kernel(DirectConvArgs a) {
     // this lane's outputs: out[y0 + 16 b + n][x0 + 16 wave + 4 kk + 0..3]
     const int x0 = (tile % tiles_x) * TILE, y0 = (tile / tiles_x) * TILE;
     const int x = x0 + wave * 16 + 4 * kk;
-    const bool vec = (a.W % 4 == 0) && (x + 3 < a.W);
+    const bool vec = a.epi_vec && (x + 3 < a.W);
     // SPLIT: the matrix phase is short, so the operands of the epilogue -- (background, counts) or (out_scale, out) -- are
     // requested before it instead of after it
     float4 e0[SPLIT ? 4 : 1], e1[SPLIT ? 4 : 1];
@@ -571,10 +573,24 @@ int launch_toeplitz_fragments(const float* psf, float* afrag_fwd, float* afrag_a
   return JD_OK;
 }
 
+// What a launch derives from the plan's geometry; jd_conv_plan_direct_kernel reports these same functions' values.
+static int direct_template_kc(int kw, int split) { return split ? 32 * direct_split_ks(kw) : direct_conv_kc(kw); }
+static int direct_ox_in(int kw, int ox, int adjoint) { return adjoint ? -ox : ox - (kw - 1); }  // adjoint: (kw - 1 - ox) - (kw - 1)
+// the window columns of every tile start on a 16-byte boundary of the image rows
+static bool direct_stage_vec_shape(int W, int ox_in) { return W % 4 == 0 && ox_in % 4 == 0; }
+static bool is_aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }  // (null is)
+
+void direct_conv_route(int W, int kw, int ox, int split, int* route4) {
+  route4[0] = direct_template_kc(kw, split);
+  route4[1] = split ? 1 : 0;
+  route4[2] = direct_stage_vec_shape(W, direct_ox_in(kw, ox, 0)) ? 1 : 0;
+  route4[3] = direct_stage_vec_shape(W, direct_ox_in(kw, ox, 1)) ? 1 : 0;
+}
+
 static int g_conv_n_cu = 0;
 
 template <int KC, bool POISSON, bool SPLIT = false>
-static int launch_kc(const DirectConvArgs& a, hipStream_t stream) {
+static int launch_kc(DirectConvArgs a, hipStream_t stream) {
   constexpr int PITCH = 48 + KC + 2, PH = 48 + KC + 8;
   const int rows = TILE - 1 + a.kh;
   const size_t lds = SPLIT ? (size_t)((rows * PH + 3) & ~3) * sizeof(float) + (size_t)a.kh * (KC / 32) * 128 * sizeof(uint4)
@@ -605,9 +621,12 @@ static int launch_kc(const DirectConvArgs& a, hipStream_t stream) {
   }
   int grid = g_conv_n_cu * per_cu;
   if (grid > n_tiles) grid = n_tiles;
-  const bool vec = (a.W % 4 == 0) && (a.ox_in % 4 == 0) &&
-                   (reinterpret_cast<uintptr_t>(a.in) % 16 == 0) &&
-                   (!a.in_scale || reinterpret_cast<uintptr_t>(a.in_scale) % 16 == 0);
+  const bool vec = direct_stage_vec_shape(a.W, a.ox_in) && is_aligned16(a.in) && is_aligned16(a.in_scale);
+  // The epilogue moves float4 too, whichever way the window was staged: the gradient image of a fit's second flux
+  // component is a slice of one flat buffer and only 4-byte aligned when the first component's pixel count is no
+  // multiple of 4 -- such a launch takes the epilogue's element-wise branch (the same arithmetic, the same bits).
+  a.epi_vec = a.W % 4 == 0 && is_aligned16(a.out) && is_aligned16(a.out_scale) && is_aligned16(a.background) && is_aligned16(a.counts) &&
+              is_aligned16(a.npred_out);
   if (vec)
     direct_conv_kernel<KC, true, POISSON, SPLIT><<<grid, 256, lds, stream>>>(a);
   else
@@ -618,8 +637,9 @@ static int launch_kc(const DirectConvArgs& a, hipStream_t stream) {
 
 template <bool POISSON>
 static int dispatch_kc(const DirectConvArgs& a, int kw, int split, hipStream_t stream) {
-  if (split) return direct_split_ks(kw) == 1 ? launch_kc<32, POISSON, true>(a, stream) : launch_kc<64, POISSON, true>(a, stream);
-  switch (direct_conv_kc(kw)) {
+  const int kc = direct_template_kc(kw, split);
+  if (split) return kc == 32 ? launch_kc<32, POISSON, true>(a, stream) : launch_kc<64, POISSON, true>(a, stream);
+  switch (kc) {
     case 16: return launch_kc<16, POISSON>(a, stream);
     case 20: return launch_kc<20, POISSON>(a, stream);
     case 24: return launch_kc<24, POISSON>(a, stream);
@@ -641,13 +661,8 @@ int launch_direct_conv(const float* in, const float* in_scale, const float* afra
   DirectConvArgs a{};
   a.in = in, a.in_scale = in_scale, a.afrag = afrag, a.out = out, a.out_scale = out_scale;
   a.H = H, a.W = W, a.kh = kh, a.coef = coef, a.accumulate = accumulate;
-  if (adjoint) {
-    a.oy = kh - 1 - oy;
-    a.ox_in = -ox;  // (kw - 1 - ox) - (kw - 1)
-  } else {
-    a.oy = oy;
-    a.ox_in = ox - (kw - 1);
-  }
+  a.oy = adjoint ? kh - 1 - oy : oy;
+  a.ox_in = direct_ox_in(kw, ox, adjoint);
   ProfScope prof(JD_KERNEL_DIRECT_CONV, stream);
   return dispatch_kc<false>(a, kw, split, stream);
 }
@@ -664,7 +679,7 @@ int launch_direct_conv_poisson(const float* in, const float* in_scale, const flo
   DirectConvArgs a{};
   a.in = in, a.in_scale = in_scale, a.afrag = afrag, a.out = g_out;
   a.H = H, a.W = W, a.kh = kh, a.coef = 1.f;
-  a.oy = oy, a.ox_in = ox - (kw - 1);
+  a.oy = oy, a.ox_in = direct_ox_in(kw, ox, 0);
   a.background = background, a.counts = counts, a.npred_out = npred_out, a.partials = partials;
   a.eps = eps, a.inv_n = inv_n, a.write_grad = write_grad;
   *n_partials = direct_conv_tiles(H, W);

@@ -928,6 +928,15 @@ extern "C" int jd_conv_plan_step_route(const jd_conv_plan* p, int upsampling, in
   return JD_OK;
 }
 
+extern "C" int jd_conv_plan_direct_kernel(const jd_conv_plan* p, int32_t* kernel4) {
+  JD_REQUIRE(p && kernel4, "jd_conv_plan_direct_kernel: null argument");
+  JD_REQUIRE(p->method == JD_CONV_DIRECT, "jd_conv_plan_direct_kernel: not a plan of the direct method");
+  int route[4];
+  direct_conv_route(p->W, p->kw, p->ox, p->split, route);  // (the arguments launch_direct_conv gets from this plan)
+  for (int i = 0; i < 4; ++i) kernel4[i] = route[i];
+  return JD_OK;
+}
+
 // The joint step over several CALIBRATED and / or UP-SAMPLED datasets of one flux component on the native FFT path
 // (include/jolideco_hip.h).  Anything else -- another method, an up-sampling factor the fused launches do not take, a
 // forward-only evaluation, switched-off fusion -- runs the per-dataset calls this stands for.

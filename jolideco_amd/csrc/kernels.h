@@ -80,6 +80,9 @@ int launch_direct_conv(const float* in, const float* in_scale, const float* afra
                        int H, int W, int kh, int kw, int oy, int ox, int adjoint, float coef, int accumulate, int split,
                        hipStream_t stream);
 int direct_conv_tiles(int H, int W);
+// {KC of the kernel instantiation, split, float4 window staging of the forward / of the adjoint launch given 16-byte aligned
+// images}: what launch_direct_conv derives from these arguments (jd_conv_plan_direct_kernel)
+void direct_conv_route(int W, int kw, int ox, int split, int* route4);
 int launch_direct_conv_poisson(const float* in, const float* in_scale, const float* afrag, float* g_out, int H, int W,
                                int kh, int kw, int oy, int ox, const float* background, const float* counts,
                                float* npred_out, double* partials, float eps, float inv_n, int write_grad,

@@ -168,6 +168,14 @@ class ConvPlan:
             "shift_bwd_rows": int(out[7]),
         }
 
+    def direct_kernel(self):
+        """The instantiation of the MFMA Toeplitz kernel a "direct" plan launches (jd_conv_plan_direct_kernel): dict of
+        ``KC`` (fp32: 16 .. 48, split: 32 or 64), ``split`` (the split-fp16 kernel, not the fp32 one) and ``vec_fwd`` /
+        ``vec_adj`` (the forward convolution / the adjoint stages 16-byte chunks when its images are 16-byte aligned)."""
+        out = (ctypes.c_int32 * 4)()
+        check(_hip.lib().jd_conv_plan_direct_kernel(self._handle, out))
+        return {"KC": int(out[0]), "split": bool(out[1]), "vec_fwd": bool(out[2]), "vec_adj": bool(out[3])}
+
     # --- kernel spectrum (once per dataset and component) -----------------------------------
     def psf_spectrum(self, psf, out=None):
         """The kernel operator of `psf` for this plan (jd_conv_psf_spectrum).  Operator buffers are immutable: to change

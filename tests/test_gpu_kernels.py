@@ -301,6 +301,10 @@ def test_direct_conv_matches_fft_and_float64(shape, kshape, direct_kernel, jd_op
     for method in ("direct", "fft", "fft-exact"):
         plan = ConvPlan(shape[0], shape[1], kh, kw, DEV, method=method)
         assert plan.method == ("direct" if method == "direct" else "fft")
+        if method == "direct":  # the kernel this parameter means (jd_conv_plan_direct_kernel)
+            route = plan.direct_kernel()
+            assert route["split"] == (direct_kernel == "split_fp16" and kshape != (33, 33))
+            assert route["KC"] == ((32 if kw <= 17 else 64) if route["split"] else (15 + kw + 3) // 4 * 4)
         khat = plan.psf_spectrum(t(psf))
         out = plan.conv_same(t(image), t(scale), khat)
         adj = plan.conv_same_adjoint(t(grad_out), t(scale), khat)
