@@ -567,6 +567,54 @@ int jd_adam_step_multi(int n_tensors, float* const* theta, const float* const* g
 int jd_sgd_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
                 const float* mask, size_t n, float lr, int zero_grad, int use_log_flux, void* stream);
 
+/* The optimizer step with the options of torch.optim.Adam / torch.optim.SGD (csrc/optimizer.hip; jolideco/core.py:39-42
+ * hands `optimizer_kwargs` to them unchanged).  Kernels of their own: jd_adam_step, jd_sgd_step and the fused steps above
+ * know no option and stay as they are.  With every option at its torch default ("off") the bits of jd_adam_step /
+ * jd_sgd_step.  Timed under JD_KERNEL_ADAM like every other step kernel.
+ *   Adam: weight_decay      g += weight_decay * theta, before the moments
+ *         decoupled_weight_decay != 0 (AdamW): theta *= 1 - lr * weight_decay instead, before the update
+ *         amsgrad != 0      max_exp_avg_sq = max(max_exp_avg_sq, exp_avg_sq) takes exp_avg_sq's place in the denominator
+ *         With any of the three the operations of a parameter run in double and every image is rounded once (the
+ *         error against torch.optim in float64 is then that of the float32 images, whatever the operation order).
+ *   SGD:  weight_decay      as above, one fused multiply-add -- SGD with options gives the bits of torch's float32 kernels
+ *         momentum          buf = first_step ? g : momentum * buf + (1 - dampening) * g;  g = nesterov ? g + momentum * buf : buf
+ *                           first_step: the first step in which the parameter has a gradient -- the buffer BECOMES the
+ *                           gradient (weight decay included, no dampening) and is not read
+ * The chain rule in front (g = grad_flux * flux_in; use_log_flux = 0: * mask) and flux_out = exp(theta) [* mask] behind are
+ * those of jd_adam_step: under a mask the flux gradient of theta is 0, weight decay moves theta all the same, the flux
+ * stays 0.  lr, weight_decay, momentum and dampening are doubles: 1 - lr * weight_decay and 1 - dampening are formed in
+ * double and rounded once, as torch does with its Python floats. */
+enum { JD_OPTIMIZER_ADAM = 0, JD_OPTIMIZER_SGD = 1 };
+typedef struct {
+  int kind;                  /* JD_OPTIMIZER_ADAM / JD_OPTIMIZER_SGD */
+  float step_size, beta1, beta2, one_minus_beta1, one_minus_beta2, bias2_sqrt, eps; /* Adam: as jd_adam_step */
+  double lr;                 /* SGD: the step; Adam: only in 1 - lr * weight_decay (step_size carries it otherwise) */
+  double weight_decay;       /* >= 0 */
+  double momentum, dampening; /* SGD; momentum >= 0 */
+  int decoupled_weight_decay; /* Adam */
+  int amsgrad;               /* Adam: needs max_exp_avg_sq */
+  int nesterov;              /* SGD: needs momentum > 0 and dampening == 0 */
+  int first_step;            /* SGD with momentum, see above (jd_optimizer_step_multi: per tensor, this one is not read) */
+} jd_optimizer_options;
+/* The images of jd_adam_step and the state images the options need: exp_avg, exp_avg_sq (Adam), max_exp_avg_sq (amsgrad),
+ * momentum_buffer (SGD with momentum != 0); the others may be NULL and are not touched.  16-byte loads and stores where n
+ * % 4 == 0 and every image is 16-byte aligned, pixel by pixel otherwise: the same bits.  bias_dev as in jd_adam_step (Adam).
+ * JD_ERR_INVALID before anything is touched: a NULL required pointer, n == 0, a missing state image, an unknown kind, a
+ * negative or non-finite lr / weight_decay / momentum, a non-finite dampening, nesterov without momentum or with
+ * dampening, an Adam option with SGD or an SGD option with Adam. */
+int jd_optimizer_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux, float* exp_avg,
+                      float* exp_avg_sq, float* max_exp_avg_sq, float* momentum_buffer, const float* mask, size_t n,
+                      const jd_optimizer_options* options, int zero_grad, int use_log_flux, const float* bias_dev,
+                      void* stream);
+/* jd_optimizer_step with use_log_flux = 0 and no mask for MANY small parameter vectors in ONE launch, as jd_adam_step_multi:
+ * host arrays of n_tensors <= 64 entries; tensor i takes step_size[i] / bias2_sqrt[i] (Adam; or bias_dev, device [2
+ * n_tensors]) and first_step[i] (SGD with momentum; NULL otherwise).  State pointer arrays an option does not need may be
+ * NULL.  Same bits as n_tensors calls of jd_optimizer_step; the same refusals, and n_tensors outside [1, 64]. */
+int jd_optimizer_step_multi(int n_tensors, float* const* theta, const float* const* grad, float* const* exp_avg,
+                            float* const* exp_avg_sq, float* const* max_exp_avg_sq, float* const* momentum_buffer,
+                            const int* sizes, const float* step_size, const float* bias2_sqrt, const int* first_step,
+                            const jd_optimizer_options* options, const float* bias_dev, void* stream);
+
 /* Sparse point-source flux component (models/core.py:54-342, utils/torch.py:31-38) ------------------------------
  * A list of n sources: param_flux[i] = log(flux_i) when use_log_flux != 0, else flux_i; x_pos[i] / y_pos[i] pixel
  * coordinates (pixel centres at integers, x indexes columns, y rows -- the reference's component compares its `x_pos` with

@@ -140,6 +140,15 @@ EXPORTS = {
         [c_int, fpp, fpp, fpp, fpp, POINTER(c_int), fp, fp, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p],
     ),
     "jd_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_int, c_int, c_void_p]),
+    "jd_optimizer_step": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int,
+         c_int, c_void_p, c_void_p],
+    ),
+    "jd_optimizer_step_multi": (
+        c_int,
+        [c_int, fpp, fpp, fpp, fpp, fpp, fpp, POINTER(c_int), fp, fp, POINTER(c_int), c_void_p, c_void_p, c_void_p],
+    ),
     "jd_sparse_max_sources": (c_int, []),
     "jd_sparse_render": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "jd_sparse_backward": (
@@ -174,6 +183,21 @@ class Step(ctypes.Structure):
         ("step_size", c_float), ("beta1", c_float), ("beta2", c_float), ("one_minus_beta1", c_float),
         ("one_minus_beta2", c_float), ("bias2_sqrt", c_float), ("eps", c_float), ("lr", c_float),
         ("use_log_flux", c_int), ("sgd", c_int), ("bias_dev", c_void_p), ("addend", c_void_p * ADDEND_MAX),
+    ]
+
+
+OPTIMIZER_ADAM, OPTIMIZER_SGD = 0, 1  # JD_OPTIMIZER_* of include/jolideco_hip.h
+
+
+class OptimizerOptions(ctypes.Structure):
+    """`jd_optimizer_options` of include/jolideco_hip.h: the optimizer step with torch.optim's options."""
+
+    _fields_ = [
+        ("kind", c_int),
+        ("step_size", c_float), ("beta1", c_float), ("beta2", c_float), ("one_minus_beta1", c_float),
+        ("one_minus_beta2", c_float), ("bias2_sqrt", c_float), ("eps", c_float),
+        ("lr", c_double), ("weight_decay", c_double), ("momentum", c_double), ("dampening", c_double),
+        ("decoupled_weight_decay", c_int), ("amsgrad", c_int), ("nesterov", c_int), ("first_step", c_int),
     ]
 
 

@@ -38,6 +38,42 @@ __all__ = ["MAPDeconvolver", "MAPDeconvolverResult", "FitSession"]
 
 OPTIMIZER = ("adam", "sgd")
 FIT_MODES = ("sequential", "joint")
+# the options of torch.optim.Adam / torch.optim.SGD the library's step takes beside lr / betas / eps, at their torch
+# defaults: "off".  Every other key of `optimizer_kwargs` (maximize, foreach, fused, capturable, differentiable ...) is refused.
+OPTIMIZER_OPTIONS = {
+    "adam": {"weight_decay": 0, "amsgrad": False, "decoupled_weight_decay": False},
+    "sgd": {"momentum": 0, "dampening": 0, "nesterov": False, "weight_decay": 0},
+}
+
+
+def optimizer_options(cfg):
+    """(options, active) of a deconvolver: its optimizer's options (`OPTIMIZER_OPTIONS`) with the values of
+    ``optimizer_kwargs``, and whether any differs from its torch default.  An active option sends every parameter through
+    `jd_optimizer_step` / `jd_optimizer_step_multi`, kernels of their own; with none the session launches what it launched
+    before the options existed, whether the keys are present or not."""
+    kwargs = getattr(cfg, "optimizer_kwargs", None) or {}
+    defaults = OPTIMIZER_OPTIONS.get(getattr(cfg, "optimizer_type", "adam"), {})
+    if not any(key in kwargs for key in defaults):  # (no key given: the epoch body asks several times per step)
+        return defaults, False
+    options = {key: kwargs.get(key, default) for key, default in defaults.items()}
+    return options, any(options[key] != default for key, default in defaults.items())
+
+
+def _options_struct(cfg, options, step_size=0.0, bias2_sqrt=1.0, first_step=False):
+    """`_hip.OptimizerOptions` of the deconvolver's optimizer for one step (the Adam bias terms by value)."""
+    lr = cfg.optimizer_kwargs["lr"]
+    out = _hip.OptimizerOptions(lr=lr, weight_decay=options["weight_decay"], first_step=int(first_step))
+    if cfg.optimizer_type == "adam":
+        beta1, beta2 = cfg.optimizer_kwargs.get("betas", (0.9, 0.999))
+        out.kind = _hip.OPTIMIZER_ADAM
+        out.step_size, out.bias2_sqrt = step_size, bias2_sqrt
+        out.beta1, out.beta2, out.one_minus_beta1, out.one_minus_beta2 = beta1, beta2, 1 - beta1, 1 - beta2
+        out.eps = cfg.optimizer_kwargs.get("eps", 1e-8)
+        out.amsgrad, out.decoupled_weight_decay = int(bool(options["amsgrad"])), int(bool(options["decoupled_weight_decay"]))
+    else:
+        out.kind = _hip.OPTIMIZER_SGD
+        out.momentum, out.dampening, out.nesterov = options["momentum"], options["dampening"], int(bool(options["nesterov"]))
+    return out
 
 
 class _ComponentState:
@@ -45,7 +81,7 @@ class _ComponentState:
     two flux buffers (current / previous, so the trace can see the pre-step flux), the flux
     gradient accumulator and the Adam moments."""
 
-    def __init__(self, name, component, grad):
+    def __init__(self, name, component, grad, options=None):
         self.name = name
         self.component = component
         theta = component._flux_upsampled.data
@@ -61,6 +97,10 @@ class _ComponentState:
         self.grad = grad.reshape(self.shape)  # view into the flat communication buffer
         self.exp_avg = torch.zeros_like(self.theta)
         self.exp_avg_sq = torch.zeros_like(self.theta)
+        # the state images of the optimizer's options (`optimizer_options`), allocated here and not in a step
+        self.max_exp_avg_sq = torch.zeros_like(self.theta) if (options or {}).get("amsgrad") else None
+        self.momentum_buffer = torch.zeros_like(self.theta) if (options or {}).get("momentum") else None
+        self.first_step = True  # (SGD with momentum: the first step makes the buffer the gradient)
         self.frozen = component.frozen
         self.use_log_flux = bool(component.use_log_flux)
         # reference quirk: with use_log_flux=False and no mask `flux_upsampled` IS the
@@ -160,7 +200,11 @@ class MAPDeconvolver:
         Show a tqdm progress bar (forces one device->host sync per epoch).
     optimizer_type : {"adam", "sgd"}
     optimizer_kwargs : dict
-        ``lr``, and for Adam ``betas`` and ``eps``.
+        ``lr``; for Adam ``betas``, ``eps``, ``weight_decay``, ``amsgrad`` and ``decoupled_weight_decay``; for SGD
+        ``momentum``, ``dampening``, ``nesterov`` and ``weight_decay`` -- validated by torch.optim itself.  An option
+        that differs from its torch default takes the fit off the fused step kernels (`optimizer_options`); a momentum
+        also off the captured epochs.  ``maximize``, ``foreach``, ``fused``, ``capturable`` and ``differentiable``
+        raise NotImplementedError.
     checkpoint_path : str
         Directory for per-epoch checkpoints (``checkpoint-epoch-<n>.asdf``, the reference's name and format,
         core.py:77,234-245).  Forces one device->host copy per epoch.
@@ -205,9 +249,15 @@ class MAPDeconvolver:
         self.optimizer_type = optimizer_type
         self.optimizer_kwargs = dict(optimizer_kwargs or {})
         self.optimizer_kwargs.setdefault("lr", self.learning_rate)
-        unknown = set(self.optimizer_kwargs) - {"lr", "betas", "eps"}
+        options = OPTIMIZER_OPTIONS[optimizer_type]
+        unknown = set(self.optimizer_kwargs) - {"lr", "betas", "eps"} - set(options)
         if unknown:
             raise NotImplementedError(f"optimizer_kwargs {sorted(unknown)} are not implemented in jolideco_amd")
+        given = {key: self.optimizer_kwargs[key] for key in options if key in self.optimizer_kwargs}
+        if given:
+            # torch.optim is the arbiter of what a value may be: its constructor, on one scalar, raises its ValueErrors
+            optimizer = torch.optim.Adam if optimizer_type == "adam" else torch.optim.SGD
+            optimizer([torch.nn.Parameter(torch.zeros(1))], lr=self.optimizer_kwargs["lr"], **given)
         if checkpoint_path is not None:
             checkpoint_path = Path(checkpoint_path)
             checkpoint_path.mkdir(exist_ok=True, parents=True)
@@ -258,6 +308,7 @@ class MAPDeconvolver:
         already applied the update (`device_fwd_bwd_step`): only their buffers are swapped."""
         lib = _hip.lib()
         lr = self.optimizer_kwargs["lr"]
+        options, with_options = optimizer_options(self)
         for ci, st in enumerate(states):
             n = st.grad.numel()
             stream = stream_ptr(st.grad.device)
@@ -269,6 +320,20 @@ class MAPDeconvolver:
             elif getattr(st, "is_sparse", False):
                 # backward to the source vectors, their optimizer step, the image of the new sources
                 st.step(step)
+            elif with_options:
+                # the step with torch.optim's options: a launch of its own (no fused form takes them)
+                terms = (0.0, 1.0)
+                if self.optimizer_type == "adam":
+                    terms = adam_bias_terms(step, lr, *self.optimizer_kwargs.get("betas", (0.9, 0.999)))
+                args = _options_struct(self, options, *terms, first_step=st.first_step)
+                check(
+                    lib.jd_optimizer_step(
+                        ptr(st.theta), ptr(st.flux_cur), ptr(st.flux[1 - st.cur]), ptr(st.grad), ptr(st.exp_avg),
+                        ptr(st.exp_avg_sq), ptr(st.max_exp_avg_sq), ptr(st.momentum_buffer), ptr(st.mask), n,
+                        ctypes.byref(args), 0, int(st.use_log_flux), ptr(getattr(st, "bias_dev", None)), stream,
+                    )
+                )
+                st.first_step = False
             elif self.optimizer_type == "adam":
                 beta1, beta2 = self.optimizer_kwargs.get("betas", (0.9, 0.999))
                 eps = self.optimizer_kwargs.get("eps", 1e-8)
@@ -472,11 +537,59 @@ def _adam_step_many(cfg, items, cache, bias_dev=None):
         ))
 
 
+def _optimizer_step_many(cfg, options, items, cache, bias_dev=None):
+    """`_adam_step_many` for an optimizer with options, Adam or SGD (jd_optimizer_step_multi): ONE launch for the small
+    parameter tensors `items` that have a gradient, each with its own step count and -- SGD with momentum -- its own first
+    step, on which the buffer becomes the gradient."""
+    adam = cfg.optimizer_type == "adam"
+    lr = cfg.optimizer_kwargs["lr"]
+    beta1, beta2 = cfg.optimizer_kwargs.get("betas", (0.9, 0.999))
+    todo = []
+    for p, st in items:
+        if p.grad is None:
+            if bias_dev is not None:
+                raise RuntimeError("planned epoch: a calibration parameter lost its gradient between two epochs")
+            continue
+        st["step"] += 1
+        todo.append((p, st))
+    lib = _hip.lib()
+    args = _options_struct(cfg, options)
+    for start in range(0, len(todo), 64):
+        part = todo[start : start + 64]
+        n = len(part)
+        key = ("options",) + tuple((p.data_ptr(), p.grad.data_ptr()) for p, _ in part)
+        arrays = cache.get(key)
+        if arrays is None:
+            if len(cache) >= 64:
+                cache.clear()
+            states = [st for _, st in part]
+            arrays = cache[key] = (
+                ptr_array([p.data for p, _ in part]), ptr_array([p.grad for p, _ in part]),
+                ptr_array([st["exp_avg"] for st in states]), ptr_array([st["exp_avg_sq"] for st in states]),
+                ptr_array([st["max_exp_avg_sq"] for st in states]) if options.get("amsgrad") else None,
+                ptr_array([st["momentum_buffer"] for st in states]) if options.get("momentum") else None,
+                (ctypes.c_int * n)(*[p.numel() for p, _ in part]),
+            )
+        terms = [adam_bias_terms(st["step"], lr, beta1, beta2) if adam else (0.0, 1.0) for _, st in part]
+        first = (ctypes.c_int * n)(*[int(st["first_step"]) for _, st in part]) if options.get("momentum") else None
+        check(lib.jd_optimizer_step_multi(
+            n, *arrays, (ctypes.c_float * n)(*[t[0] for t in terms]), (ctypes.c_float * n)(*[t[1] for t in terms]), first,
+            ctypes.byref(args), None if bias_dev is None or not adam else ptr(bias_dev[2 * start : 2 * (start + n)]),
+            stream_ptr(part[0][0].device),
+        ))
+        for _, st in part:
+            st["first_step"] = False
+
+
 def _step_parameters(cfg, items, cache, bias_dev=None):
     """The optimizer step of the small parameter tensors `items` = [(parameter, state)]: calibration parameters, the source
     vectors of a sparse component.  A parameter whose ``grad`` is None takes no step and its count stays (torch.optim skips
     it: jolideco/core.py:197-204,229).  Adam: one launch for all of them (`_adam_step_many`; ``bias_dev``: the device bias
-    terms of a planned epoch).  SGD: `jd_sgd_step` with ``use_log_flux=0``, the plain update of a parameter vector."""
+    terms of a planned epoch).  SGD: `jd_sgd_step` with ``use_log_flux=0``, the plain update of a parameter vector.  With
+    an option of torch.optim active (`optimizer_options`), either optimizer: one launch (`_optimizer_step_many`)."""
+    options, with_options = optimizer_options(cfg)
+    if with_options:
+        return _optimizer_step_many(cfg, options, items, cache, bias_dev)
     if cfg.optimizer_type == "adam":
         return _adam_step_many(cfg, items, cache, bias_dev)
     lr = cfg.optimizer_kwargs["lr"]
@@ -501,6 +614,12 @@ class _CalibrationStepper:
         self.state = [
             {"step": 0, "exp_avg": torch.zeros_like(p.data), "exp_avg_sq": torch.zeros_like(p.data)} for p in self.params
         ]
+        options, _ = optimizer_options(deconvolver)
+        for p, state in zip(self.params, self.state):  # (the state of the options: allocated here, not in a step)
+            if options.get("amsgrad"):
+                state["max_exp_avg_sq"] = torch.zeros_like(p.data)
+            if options.get("momentum"):
+                state["momentum_buffer"], state["first_step"] = torch.zeros_like(p.data), True
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
@@ -681,7 +800,8 @@ class FitSession:
         offsets = np.concatenate([[0], np.cumsum(numels)])
         self.states = [
             _SparseComponentState(name, comp, self.comm[offsets[i] : offsets[i + 1]], deconvolver)
-            if getattr(comp, "is_sparse", False) else _ComponentState(name, comp, self.comm[offsets[i] : offsets[i + 1]])
+            if getattr(comp, "is_sparse", False)
+            else _ComponentState(name, comp, self.comm[offsets[i] : offsets[i + 1]], optimizer_options(deconvolver)[0])
             for i, (name, comp) in enumerate(components.items())
         ]
         self.scalars = self.comm[offsets[-1] :]
@@ -867,9 +987,11 @@ class FitSession:
     def _fuse_step(self, st, prior):
         """The prior of this component applies the optimizer step itself (`device_fwd_bwd_step`): single process (the
         gradient buffer is complete when the prior runs), not frozen, a prior that supports it, stride >= 4, and the
-        session's own `_optimizer_step` (tests that replace it to record or suppress the step see every gradient)."""
+        session's own `_optimizer_step` (tests that replace it to record or suppress the step see every gradient), and no
+        active option of torch.optim (`optimizer_options`: the fused kernels know none)."""
         return (
             self.fuse_optimizer_step and not self.dist.sharded and not st.frozen
+            and not optimizer_options(self.cfg)[1]  # (an option of torch.optim: the step is a launch of its own)
             and not getattr(st, "is_sparse", False)  # (a sparse component steps its source vectors, not an image)
             and getattr(prior, "supports_fused_step", False) and getattr(prior, "stride", 0) >= 4
             and "_optimizer_step" not in vars(self.cfg)  # (a hook installed on the instance AFTER the session was built)
@@ -878,7 +1000,9 @@ class FitSession:
     def _fuse_band_step(self, st):
         """Sharded fits: the bands of the prior's gradient are added and the optimizer step applied in one launch
         (jd_add_rolled_bands_step) -- not frozen, width a multiple of 4 and 16-byte aligned images, the session's own
-        `_optimizer_step`, no JOLIDECO_NO_FUSED_STEP."""
+        `_optimizer_step`, no JOLIDECO_NO_FUSED_STEP, no active option of torch.optim (`optimizer_options`)."""
+        if optimizer_options(self.cfg)[1]:
+            return False
         if st.frozen or getattr(st, "is_sparse", False) or not self.fuse_optimizer_step or "_optimizer_step" in vars(self.cfg):
             return False
         images = [st.theta, st.flux[0], st.flux[1], st.grad, getattr(st, "exp_avg", None), getattr(st, "exp_avg_sq", None), st.mask]
@@ -923,10 +1047,15 @@ class FitSession:
         """Planned epochs apply: one process, the session's own optimizer step (a hook sees every gradient through the
         by-value path), no event brackets around collectives, no kernel timers, no sparse component (its stepper takes
         its bias terms by value: by-value epochs only, nothing is captured) and no multi-scale prior (a draw is one pair
-        per level on grids of different sizes: a captured epoch would bake them in)."""
+        per level on grids of different sizes: a captured epoch would bake them in).  The options of torch.optim keep
+        planned and captured epochs -- `jd_optimizer_step` reads the bias terms from device memory like `jd_adam_step` --
+        except a momentum (SGD): the first step of a parameter makes the buffer the gradient, later ones read it, and a
+        replayed launch cannot know which it is; a session with ``momentum != 0`` runs by-value epochs only."""
         if self.has_sparse or getattr(self, "has_multiscale", False):
             return False
         cfg = self.cfg
+        if optimizer_options(cfg)[0].get("momentum"):
+            return False
         own = getattr(type(cfg), "_optimizer_step", None) is MAPDeconvolver._optimizer_step and "_optimizer_step" not in vars(cfg)
         return (self._planned_ok and own and not self.dist.sharded and self.comm_events is None and not self.n_val
                 and cfg.optimizer_type in ("adam", "sgd"))
@@ -1039,6 +1168,8 @@ class FitSession:
             return None
         st, prior = self.states[0], self.priors[0]
         if st.frozen or getattr(st, "is_sparse", False) or "_optimizer_step" in vars(self.cfg):
+            return None
+        if optimizer_options(self.cfg)[1]:  # (the stand-alone step with options reads ONE gradient image)
             return None
         # Only where a prior's first phase really runs beside the likelihood launches of this step.  With nothing beside them
         # (the prior behind the likelihood, a prior without kernels, a by-value epoch) the two adjoints side by side end
