@@ -568,9 +568,10 @@ int jd_sgd_step(float* theta, const float* flux_in, float* flux_out, float* grad
                 const float* mask, size_t n, float lr, int zero_grad, int use_log_flux, void* stream);
 
 /* The optimizer step with the options of torch.optim.Adam / torch.optim.SGD (csrc/optimizer.hip; jolideco/core.py:39-42
- * hands `optimizer_kwargs` to them unchanged).  Kernels of their own: jd_adam_step, jd_sgd_step and the fused steps above
- * know no option and stay as they are.  With every option at its torch default ("off") the bits of jd_adam_step /
- * jd_sgd_step.  Timed under JD_KERNEL_ADAM like every other step kernel.
+ * hands `optimizer_kwargs` to them unchanged).  One kernel family and one launcher with jd_adam_step, jd_adam_step_addends
+ * and jd_sgd_step, which are this entry with every option at its torch default ("off"): the library picks the kernel from
+ * the options, and with none it is the plain float32 step, the same launch and the same bits.  The fused steps above know
+ * no option.  Timed under JD_KERNEL_ADAM like every other step kernel.
  *   Adam: weight_decay      g += weight_decay * theta, before the moments
  *         decoupled_weight_decay != 0 (AdamW): theta *= 1 - lr * weight_decay instead, before the update
  *         amsgrad != 0      max_exp_avg_sq = max(max_exp_avg_sq, exp_avg_sq) takes exp_avg_sq's place in the denominator
@@ -606,10 +607,11 @@ int jd_optimizer_step(float* theta, const float* flux_in, float* flux_out, float
                       float* exp_avg_sq, float* max_exp_avg_sq, float* momentum_buffer, const float* mask, size_t n,
                       const jd_optimizer_options* options, int zero_grad, int use_log_flux, const float* bias_dev,
                       void* stream);
-/* jd_optimizer_step with use_log_flux = 0 and no mask for MANY small parameter vectors in ONE launch, as jd_adam_step_multi:
- * host arrays of n_tensors <= 64 entries; tensor i takes step_size[i] / bias2_sqrt[i] (Adam; or bias_dev, device [2
- * n_tensors]) and first_step[i] (SGD with momentum; NULL otherwise).  State pointer arrays an option does not need may be
- * NULL.  Same bits as n_tensors calls of jd_optimizer_step; the same refusals, and n_tensors outside [1, 64]. */
+/* jd_optimizer_step with use_log_flux = 0 and no mask for MANY small parameter vectors in ONE launch (jd_adam_step_multi is
+ * this entry for Adam with no option: the same kernel): host arrays of n_tensors <= 64 entries; tensor i takes
+ * step_size[i] / bias2_sqrt[i] (Adam; or bias_dev, device [2 n_tensors]) and first_step[i] (SGD with momentum; NULL
+ * otherwise).  State pointer arrays an option does not need may be NULL.  Same bits as n_tensors calls of
+ * jd_optimizer_step; the same refusals, and n_tensors outside [1, 64]. */
 int jd_optimizer_step_multi(int n_tensors, float* const* theta, const float* const* grad, float* const* exp_avg,
                             float* const* exp_avg_sq, float* const* max_exp_avg_sq, float* const* momentum_buffer,
                             const int* sizes, const float* step_size, const float* bias2_sqrt, const int* first_step,

@@ -48,9 +48,10 @@ OPTIMIZER_OPTIONS = {
 
 def optimizer_options(cfg):
     """(options, active) of a deconvolver: its optimizer's options (`OPTIMIZER_OPTIONS`) with the values of
-    ``optimizer_kwargs``, and whether any differs from its torch default.  An active option sends every parameter through
-    `jd_optimizer_step` / `jd_optimizer_step_multi`, kernels of their own; with none the session launches what it launched
-    before the options existed, whether the keys are present or not."""
+    ``optimizer_kwargs``, and whether any differs from its torch default.  Every stand-alone step goes through
+    `jd_optimizer_step` / `jd_optimizer_step_multi`, which pick the kernel from the options; the steps fused into a prior's
+    kernel, the band sum and the addend images know none, so an active option switches those off (and a momentum the
+    planned epochs).  With none active the session is the same whether the keys are present or not."""
     kwargs = getattr(cfg, "optimizer_kwargs", None) or {}
     defaults = OPTIMIZER_OPTIONS.get(getattr(cfg, "optimizer_type", "adam"), {})
     if not any(key in kwargs for key in defaults):  # (no key given: the epoch body asks several times per step)
@@ -59,16 +60,22 @@ def optimizer_options(cfg):
     return options, any(options[key] != default for key, default in defaults.items())
 
 
+def _hyper_parameters(cfg):
+    """(lr, beta1, beta2, eps) of a deconvolver's optimizer, torch.optim.Adam's defaults where a key is not given."""
+    kwargs = cfg.optimizer_kwargs
+    beta1, beta2 = kwargs.get("betas", (0.9, 0.999))
+    return kwargs["lr"], beta1, beta2, kwargs.get("eps", 1e-8)
+
+
 def _options_struct(cfg, options, step_size=0.0, bias2_sqrt=1.0, first_step=False):
     """`_hip.OptimizerOptions` of the deconvolver's optimizer for one step (the Adam bias terms by value)."""
-    lr = cfg.optimizer_kwargs["lr"]
+    lr, beta1, beta2, eps = _hyper_parameters(cfg)
     out = _hip.OptimizerOptions(lr=lr, weight_decay=options["weight_decay"], first_step=int(first_step))
     if cfg.optimizer_type == "adam":
-        beta1, beta2 = cfg.optimizer_kwargs.get("betas", (0.9, 0.999))
         out.kind = _hip.OPTIMIZER_ADAM
         out.step_size, out.bias2_sqrt = step_size, bias2_sqrt
         out.beta1, out.beta2, out.one_minus_beta1, out.one_minus_beta2 = beta1, beta2, 1 - beta1, 1 - beta2
-        out.eps = cfg.optimizer_kwargs.get("eps", 1e-8)
+        out.eps = eps
         out.amsgrad, out.decoupled_weight_decay = int(bool(options["amsgrad"])), int(bool(options["decoupled_weight_decay"]))
     else:
         out.kind = _hip.OPTIMIZER_SGD
@@ -282,7 +289,7 @@ class MAPDeconvolver:
         """`_hip.Step` of component state ``st`` for optimizer step number ``step``: what a prior needs to apply the
         update in the epilogue of its own last kernel (`device_fwd_bwd_step`).  ``bias_dev``: device tensor [step_size,
         bias2_sqrt] the kernel reads instead of the by-value terms (planned epochs)."""
-        lr = self.optimizer_kwargs["lr"]
+        lr, beta1, beta2, eps = _hyper_parameters(self)
         args = _hip.Step()
         args.theta, args.flux_in, args.flux_out = st.theta.data_ptr(), st.flux_cur.data_ptr(), st.flux[1 - st.cur].data_ptr()
         args.grad_flux = st.grad.data_ptr()
@@ -291,10 +298,9 @@ class MAPDeconvolver:
         args.mask = None if st.mask is None else st.mask.data_ptr()
         args.use_log_flux = int(st.use_log_flux)
         if self.optimizer_type == "adam":
-            beta1, beta2 = self.optimizer_kwargs.get("betas", (0.9, 0.999))
             args.step_size, args.bias2_sqrt = adam_bias_terms(step, lr, beta1, beta2)
             args.beta1, args.beta2, args.one_minus_beta1, args.one_minus_beta2 = beta1, beta2, 1 - beta1, 1 - beta2
-            args.eps = self.optimizer_kwargs.get("eps", 1e-8)
+            args.eps = eps
             args.exp_avg, args.exp_avg_sq = st.exp_avg.data_ptr(), st.exp_avg_sq.data_ptr()
             args.sgd = 0
             args.bias_dev = None if bias_dev is None else bias_dev.data_ptr()
@@ -307,8 +313,9 @@ class MAPDeconvolver:
         buffers so `flux_prev` is the flux the step was computed with.  ``stepped``: components whose prior has
         already applied the update (`device_fwd_bwd_step`): only their buffers are swapped."""
         lib = _hip.lib()
-        lr = self.optimizer_kwargs["lr"]
-        options, with_options = optimizer_options(self)
+        lr, beta1, beta2, _ = _hyper_parameters(self)
+        terms = adam_bias_terms(step, lr, beta1, beta2) if self.optimizer_type == "adam" else (0.0, 1.0)
+        args = _options_struct(self, optimizer_options(self)[0], *terms)
         for ci, st in enumerate(states):
             n = st.grad.numel()
             stream = stream_ptr(st.grad.device)
@@ -320,39 +327,19 @@ class MAPDeconvolver:
             elif getattr(st, "is_sparse", False):
                 # backward to the source vectors, their optimizer step, the image of the new sources
                 st.step(step)
-            elif with_options:
-                # the step with torch.optim's options: a launch of its own (no fused form takes them)
-                terms = (0.0, 1.0)
-                if self.optimizer_type == "adam":
-                    terms = adam_bias_terms(step, lr, *self.optimizer_kwargs.get("betas", (0.9, 0.999)))
-                args = _options_struct(self, options, *terms, first_step=st.first_step)
+            else:
+                # the library picks the kernel from the options: with every one at its default the plain Adam / SGD step
+                args.first_step = int(st.first_step)
                 check(
                     lib.jd_optimizer_step(
                         ptr(st.theta), ptr(st.flux_cur), ptr(st.flux[1 - st.cur]), ptr(st.grad), ptr(st.exp_avg),
                         ptr(st.exp_avg_sq), ptr(st.max_exp_avg_sq), ptr(st.momentum_buffer), ptr(st.mask), n,
-                        ctypes.byref(args), 0, int(st.use_log_flux), ptr(getattr(st, "bias_dev", None)), stream,
-                    )
-                )
-                st.first_step = False
-            elif self.optimizer_type == "adam":
-                beta1, beta2 = self.optimizer_kwargs.get("betas", (0.9, 0.999))
-                eps = self.optimizer_kwargs.get("eps", 1e-8)
-                step_size, bias2_sqrt = adam_bias_terms(step, lr, beta1, beta2)
-                check(
-                    lib.jd_adam_step(
-                        ptr(st.theta), ptr(st.flux_cur), ptr(st.flux[1 - st.cur]), ptr(st.grad), ptr(st.exp_avg),
-                        ptr(st.exp_avg_sq), ptr(st.mask), n, step_size, beta1, beta2, 1 - beta1, 1 - beta2, bias2_sqrt, eps,
+                        ctypes.byref(args),
                         0,  # no zeroing pass: the first gradient term of every step OVERWRITES the buffer (FitSession.epoch)
                         int(st.use_log_flux), ptr(getattr(st, "bias_dev", None)), stream,
                     )
                 )
-            else:
-                check(
-                    lib.jd_sgd_step(
-                        ptr(st.theta), ptr(st.flux_cur), ptr(st.flux[1 - st.cur]), ptr(st.grad), ptr(st.mask), n, lr,
-                        0, int(st.use_log_flux), stream,
-                    )
-                )
+                st.first_step = False
             st.cur = 1 - st.cur
 
     def _as_components(self, components):
@@ -498,56 +485,21 @@ class MAPDeconvolver:
             total_loss.poisson_loss.names_all = local
 
 
-def _adam_step_many(cfg, items, cache, bias_dev=None):
-    """ONE launch for the Adam steps of the small parameter tensors `items` = [(parameter, state)] that have a gradient
-    (jd_adam_step_multi: each tensor with its own step count); `cache`: pointer arrays by tensor set.
-    ``bias_dev`` (planned epochs, `FitSession._epoch_planned`): device tensor of 2 floats per item holding the bias terms
-    of this step -- every item steps, and the kernel reads its terms from there."""
-    import ctypes
-
-    lr = cfg.optimizer_kwargs["lr"]
-    beta1, beta2 = cfg.optimizer_kwargs.get("betas", (0.9, 0.999))
+def _step_parameters(cfg, items, cache, bias_dev=None):
+    """The optimizer step of the small parameter tensors `items` = [(parameter, state)]: calibration parameters, the source
+    vectors of a sparse component.  A parameter whose ``grad`` is None takes no step and its count stays (torch.optim skips
+    it: jolideco/core.py:197-204,229).  Adam or SGD, with or without options (`optimizer_options`): ONE launch per 64
+    tensors (jd_optimizer_step_multi), each tensor with its own step count and -- SGD with momentum -- its own first step,
+    on which the buffer becomes the gradient.  `cache`: pointer arrays by tensor set.  ``bias_dev`` (planned epochs of
+    Adam, `FitSession._plan_epoch`): device tensor of 2 floats per item holding the bias terms of this step -- every item
+    steps, and the kernel reads its terms from there."""
+    options, _ = optimizer_options(cfg)
+    adam = cfg.optimizer_type == "adam"
+    lr, beta1, beta2, _ = _hyper_parameters(cfg)
     todo = []
     for p, st in items:
         if p.grad is None:
             if bias_dev is not None:  # (the plan listed the parameters that had a gradient after the previous epoch)
-                raise RuntimeError("planned epoch: a calibration parameter lost its gradient between two epochs")
-            continue
-        st["step"] += 1
-        todo.append((p, st, adam_bias_terms(st["step"], lr, beta1, beta2)))
-    lib = _hip.lib()
-    for start in range(0, len(todo), 64):
-        part = todo[start : start + 64]
-        n = len(part)
-        # (the pointer arrays of an unchanged set of tensors are built once: gradients live in persistent buffers)
-        key = tuple((p.data_ptr(), p.grad.data_ptr()) for p, _, _ in part)
-        arrays = cache.get(key)
-        if arrays is None:
-            if len(cache) >= 64:  # (a fit has a handful of tensor sets; gradients re-allocated every step must not pile up)
-                cache.clear()
-            arrays = cache[key] = (
-                ptr_array([p.data for p, _, _ in part]), ptr_array([p.grad for p, _, _ in part]),
-                ptr_array([st["exp_avg"] for _, st, _ in part]), ptr_array([st["exp_avg_sq"] for _, st, _ in part]),
-                (ctypes.c_int * n)(*[p.numel() for p, _, _ in part]),
-            )
-        check(lib.jd_adam_step_multi(
-            n, *arrays, (ctypes.c_float * n)(*[b[0] for _, _, b in part]), (ctypes.c_float * n)(*[b[1] for _, _, b in part]),
-            beta1, beta2, 1 - beta1, 1 - beta2, cfg.optimizer_kwargs.get("eps", 1e-8),
-            None if bias_dev is None else ptr(bias_dev[2 * start : 2 * (start + n)]), stream_ptr(part[0][0].device),
-        ))
-
-
-def _optimizer_step_many(cfg, options, items, cache, bias_dev=None):
-    """`_adam_step_many` for an optimizer with options, Adam or SGD (jd_optimizer_step_multi): ONE launch for the small
-    parameter tensors `items` that have a gradient, each with its own step count and -- SGD with momentum -- its own first
-    step, on which the buffer becomes the gradient."""
-    adam = cfg.optimizer_type == "adam"
-    lr = cfg.optimizer_kwargs["lr"]
-    beta1, beta2 = cfg.optimizer_kwargs.get("betas", (0.9, 0.999))
-    todo = []
-    for p, st in items:
-        if p.grad is None:
-            if bias_dev is not None:
                 raise RuntimeError("planned epoch: a calibration parameter lost its gradient between two epochs")
             continue
         st["step"] += 1
@@ -557,10 +509,11 @@ def _optimizer_step_many(cfg, options, items, cache, bias_dev=None):
     for start in range(0, len(todo), 64):
         part = todo[start : start + 64]
         n = len(part)
-        key = ("options",) + tuple((p.data_ptr(), p.grad.data_ptr()) for p, _ in part)
+        # (the pointer arrays of an unchanged set of tensors are built once: gradients live in persistent buffers)
+        key = tuple((p.data_ptr(), p.grad.data_ptr()) for p, _ in part)
         arrays = cache.get(key)
         if arrays is None:
-            if len(cache) >= 64:
+            if len(cache) >= 64:  # (a fit has a handful of tensor sets; gradients re-allocated every step must not pile up)
                 cache.clear()
             states = [st for _, st in part]
             arrays = cache[key] = (
@@ -577,34 +530,15 @@ def _optimizer_step_many(cfg, options, items, cache, bias_dev=None):
             ctypes.byref(args), None if bias_dev is None or not adam else ptr(bias_dev[2 * start : 2 * (start + n)]),
             stream_ptr(part[0][0].device),
         ))
-        for _, st in part:
-            st["first_step"] = False
-
-
-def _step_parameters(cfg, items, cache, bias_dev=None):
-    """The optimizer step of the small parameter tensors `items` = [(parameter, state)]: calibration parameters, the source
-    vectors of a sparse component.  A parameter whose ``grad`` is None takes no step and its count stays (torch.optim skips
-    it: jolideco/core.py:197-204,229).  Adam: one launch for all of them (`_adam_step_many`; ``bias_dev``: the device bias
-    terms of a planned epoch).  SGD: `jd_sgd_step` with ``use_log_flux=0``, the plain update of a parameter vector.  With
-    an option of torch.optim active (`optimizer_options`), either optimizer: one launch (`_optimizer_step_many`)."""
-    options, with_options = optimizer_options(cfg)
-    if with_options:
-        return _optimizer_step_many(cfg, options, items, cache, bias_dev)
-    if cfg.optimizer_type == "adam":
-        return _adam_step_many(cfg, items, cache, bias_dev)
-    lr = cfg.optimizer_kwargs["lr"]
-    for p, st in items:
-        if p.grad is None:
-            continue
-        st["step"] += 1
-        data = p.data
-        check(_hip.lib().jd_sgd_step(ptr(data), ptr(data), ptr(data), ptr(p.grad), None, p.numel(), lr, 0, 0, stream_ptr(p.device)))
+        if first is not None:
+            for _, st in part:
+                st["first_step"] = False
 
 
 class _CalibrationStepper:
     """The optimizer of ONE dataset's calibration parameters (a (1, 2) shift and a (1,) log background norm) on the
-    library's step kernel: `jd_adam_step` / `jd_sgd_step` with ``use_log_flux=0`` is the plain `torch.optim.Adam` /
-    `SGD` update of a parameter vector (per-parameter state and step count, a parameter whose ``grad`` is None is
+    library's many-vector step kernel (`_step_parameters`): the `torch.optim.Adam` / `SGD` update of a parameter vector,
+    the library's image step with ``use_log_flux=0`` (per-parameter state and step count, a parameter whose ``grad`` is None is
     skipped -- jolideco/core.py:197-204,229).  A `torch.optim` step on two tiny device tensors costs the host ~0.5 ms
     (a dozen launches each); eight calibrated observations made the step host bound (bench config c6)."""
 
@@ -1048,7 +982,7 @@ class FitSession:
         by-value path), no event brackets around collectives, no kernel timers, no sparse component (its stepper takes
         its bias terms by value: by-value epochs only, nothing is captured) and no multi-scale prior (a draw is one pair
         per level on grids of different sizes: a captured epoch would bake them in).  The options of torch.optim keep
-        planned and captured epochs -- `jd_optimizer_step` reads the bias terms from device memory like `jd_adam_step` --
+        planned and captured epochs -- `jd_optimizer_step` reads the bias terms from device memory like the fused steps --
         except a momentum (SGD): the first step of a parameter makes the buffer the gradient, later ones read it, and a
         replayed launch cannot know which it is; a session with ``momentum != 0`` runs by-value epochs only."""
         if self.has_sparse or getattr(self, "has_multiscale", False):
@@ -1095,8 +1029,7 @@ class FitSession:
         if self.step_scalars is None:
             self.step_scalars = StepScalars(self.comm.device, n_shift, n_flux + n_cal)
         sc = self.step_scalars
-        lr = cfg.optimizer_kwargs["lr"]
-        beta1, beta2 = cfg.optimizer_kwargs.get("betas", (0.9, 0.999))
+        lr, beta1, beta2, _ = _hyper_parameters(cfg)
         adam = cfg.optimizer_type == "adam"
         n_eval = 1 if self.joint else len(self.local_idx) + 1
         shifts_host, shifts = [], []

@@ -1,6 +1,6 @@
 // HBM-bound element-wise kernels of the MAP step (gfx950): pad*exposure (K1), k-space complex
-// multiply (K2), fused clip + background + Poisson NLL + gradient (K3), adjoint epilogue (K5),
-// exp/chain-rule + Adam/SGD (K6) and the element-wise priors.  All are streaming kernels:
+// multiply (K2), fused clip + background + Poisson NLL + gradient (K3), adjoint epilogue (K5)
+// and the element-wise priors (the optimizer step, K6, is optimizer.hip).  All are streaming kernels:
 // one pass over each operand, 16 B per lane where the row alignment allows it, fp64 block
 // partials + a single fixed-order finalize for every scalar so results are run-to-run identical.
 #include <cstdint>
@@ -8,7 +8,6 @@
 
 #include "jd_common.h"
 #include "kernels.h"
-#include "jd_adam.h"
 
 namespace jd {
 
@@ -641,96 +640,6 @@ __global__ __launch_bounds__(BLOCK) void poisson_nll_kernel(const float* __restr
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
-// ------------------------------------------------------------------------------------------
-// K6: chain rule + Adam (torch.optim.Adam single-tensor formula) + exp of the new theta
-// ------------------------------------------------------------------------------------------
-// NA: addend images (a.addend[0 .. NA) are set), added to the gradient in order before the update (jd_adam.h)
-template <int VEC, int NA>
-__global__ __launch_bounds__(BLOCK) void adam_kernel(AdamArgs a) {
-  use_device_bias(a);
-  const size_t stride = (size_t)gridDim.x * BLOCK * VEC;
-  for (size_t i = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * VEC; i < a.n; i += stride) {
-    float th[VEC], f[VEC], gf[VEC], m[VEC], v[VEC], mk[VEC];
-    if constexpr (VEC == 4) {
-      const float4 t4 = *reinterpret_cast<const float4*>(a.theta + i);
-      const float4 f4 = *reinterpret_cast<const float4*>(a.flux_in + i);
-      const float4 g4 = *reinterpret_cast<const float4*>(a.grad_flux + i);
-      float4 a4[NA ? NA : 1];
-#pragma unroll
-      for (int k = 0; k < NA; ++k) a4[k] = *reinterpret_cast<const float4*>(a.addend[k] + i);
-      th[0] = t4.x, th[1] = t4.y, th[2] = t4.z, th[3] = t4.w;
-      f[0] = f4.x, f[1] = f4.y, f[2] = f4.z, f[3] = f4.w;
-      gf[0] = g4.x, gf[1] = g4.y, gf[2] = g4.z, gf[3] = g4.w;
-      if (!a.sgd) {
-        const float4 m4 = *reinterpret_cast<const float4*>(a.m + i);
-        const float4 v4 = *reinterpret_cast<const float4*>(a.v + i);
-        m[0] = m4.x, m[1] = m4.y, m[2] = m4.z, m[3] = m4.w;
-        v[0] = v4.x, v[1] = v4.y, v[2] = v4.z, v[3] = v4.w;
-      }
-      mk[0] = mk[1] = mk[2] = mk[3] = 1.f;
-      if (a.mask) {
-        const float4 k4 = *reinterpret_cast<const float4*>(a.mask + i);
-        mk[0] = k4.x, mk[1] = k4.y, mk[2] = k4.z, mk[3] = k4.w;
-      }
-#pragma unroll
-      for (int k = 0; k < NA; ++k) gf[0] += a4[k].x, gf[1] += a4[k].y, gf[2] += a4[k].z, gf[3] += a4[k].w;
-    } else {
-      th[0] = a.theta[i], f[0] = a.flux_in[i], gf[0] = a.grad_flux[i];
-#pragma unroll
-      for (int k = 0; k < NA; ++k) gf[0] += a.addend[k][i];
-      if (!a.sgd) m[0] = a.m[i], v[0] = a.v[i];
-      mk[0] = a.mask ? a.mask[i] : 1.f;
-    }
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) adam_pixel(th[k], f[k], m[k], v[k], gf[k], mk[k], a);
-    if constexpr (VEC == 4) {
-      *reinterpret_cast<float4*>(a.theta + i) = make_float4(th[0], th[1], th[2], th[3]);
-      *reinterpret_cast<float4*>(a.flux_out + i) = make_float4(f[0], f[1], f[2], f[3]);
-      if (!a.sgd) {
-        *reinterpret_cast<float4*>(a.m + i) = make_float4(m[0], m[1], m[2], m[3]);
-        *reinterpret_cast<float4*>(a.v + i) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-      if (a.zero_grad) *reinterpret_cast<float4*>(a.grad_flux + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-      a.theta[i] = th[0], a.flux_out[i] = f[0];
-      if (!a.sgd) a.m[i] = m[0], a.v[i] = v[0];
-      if (a.zero_grad) a.grad_flux[i] = 0.f;
-    }
-  }
-}
-
-template <int NA>
-static void launch_adam_kernel(bool vec, unsigned blocks, const AdamArgs& a, hipStream_t stream) {
-  if (vec)
-    adam_kernel<4, NA><<<blocks, BLOCK, 0, stream>>>(a);
-  else
-    adam_kernel<1, NA><<<blocks, BLOCK, 0, stream>>>(a);
-}
-
-static int launch_adam(const AdamArgs& a, hipStream_t stream) {
-  int na = 0;
-  while (na < ADDEND_MAX && a.addend[na]) ++na;
-  // float4 accesses: every image the kernel touches is 16-byte aligned (null m, v, mask count as aligned), else pixel by pixel
-  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
-  bool vec = (a.n % 4 == 0) && aligned(a.theta) && aligned(a.flux_in) && aligned(a.flux_out) && aligned(a.grad_flux) &&
-             aligned(a.m) && aligned(a.v) && aligned(a.mask);
-  for (int k = 0; k < na; ++k) vec = vec && aligned(a.addend[k]);
-  const size_t per_block = (size_t)BLOCK * (vec ? 4 : 1);
-  size_t blocks = (a.n + per_block - 1) / per_block;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks == 0) blocks = 1;
-  ProfScope prof(JD_KERNEL_ADAM, stream);
-  switch (na) {
-    case 0: launch_adam_kernel<0>(vec, (unsigned)blocks, a, stream); break;
-    case 1: launch_adam_kernel<1>(vec, (unsigned)blocks, a, stream); break;
-    case 2: launch_adam_kernel<2>(vec, (unsigned)blocks, a, stream); break;
-    case 3: launch_adam_kernel<3>(vec, (unsigned)blocks, a, stream); break;
-    default: launch_adam_kernel<4>(vec, (unsigned)blocks, a, stream); break;
-  }
-  JD_LAUNCH_CHECK();
-  return JD_OK;
-}
-
 __global__ __launch_bounds__(BLOCK) void flux_from_theta_kernel(const float* __restrict__ theta,
                                                                const float* __restrict__ mask,
                                                                float* __restrict__ flux, size_t n, int linear) {
@@ -1158,98 +1067,6 @@ extern "C" int jd_step_scalars_fetch(const int32_t* host_row, int32_t* dst, int 
   fetch_scalars_kernel<<<1, 256, 0, as_stream(stream)>>>(host_row, dst, n);
   JD_LAUNCH_CHECK();
   return JD_OK;
-}
-
-extern "C" int jd_adam_step_addends(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
-                                    float* exp_avg, float* exp_avg_sq, const float* mask, size_t n, float step_size,
-                                    float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
-                                    float bias2_sqrt, float eps, int zero_grad, int use_log_flux, const float* bias_dev,
-                                    const float* const* addends, void* stream) {
-  JD_REQUIRE(theta && flux_in && flux_out && grad_flux && exp_avg && exp_avg_sq && n > 0,
-             "jd_adam_step: null argument or n == 0");
-  AdamArgs a{theta, flux_in, flux_out, grad_flux, exp_avg, exp_avg_sq, mask, n,
-             step_size, beta1, beta2, one_minus_beta1, one_minus_beta2, bias2_sqrt, eps, 0.f, zero_grad, 0,
-             use_log_flux ? 0 : 1, bias_dev};
-  static_assert(ADDEND_MAX == JD_ADDEND_MAX, "the host array of jd_adam_step_addends and AdamArgs::addend");
-  for (int k = 0; addends && k < ADDEND_MAX && addends[k]; ++k) a.addend[k] = addends[k];  // (the leading non-null entries)
-  return launch_adam(a, as_stream(stream));
-}
-
-extern "C" int jd_adam_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
-                            float* exp_avg, float* exp_avg_sq, const float* mask, size_t n, float step_size,
-                            float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
-                            float bias2_sqrt, float eps, int zero_grad, int use_log_flux, const float* bias_dev,
-                            void* stream) {
-  return jd_adam_step_addends(theta, flux_in, flux_out, grad_flux, exp_avg, exp_avg_sq, mask, n, step_size, beta1, beta2,
-                              one_minus_beta1, one_minus_beta2, bias2_sqrt, eps, zero_grad, use_log_flux, bias_dev, nullptr,
-                              stream);
-}
-
-// Adam steps of MANY small parameter vectors in one launch (the calibration parameters of the datasets of a joint step:
-// two tensors of 2 and 1 floats per dataset -- one launch each took 4.5 us, sixteen per step of eight observations).
-// One block per tensor; the update is jd_adam_step's with use_log_flux = 0 (adam_update: the same device function).
-constexpr int ADAM_MULTI_MAX = 64;
-struct AdamMultiArgs {
-  float* theta[ADAM_MULTI_MAX];
-  const float* grad[ADAM_MULTI_MAX];
-  float* m[ADAM_MULTI_MAX];
-  float* v[ADAM_MULTI_MAX];
-  int size[ADAM_MULTI_MAX];
-  float step_size[ADAM_MULTI_MAX], bias2_sqrt[ADAM_MULTI_MAX];
-  float beta1, beta2, one_minus_beta1, one_minus_beta2, eps;
-  const float* bias_dev;  // nullable, device [2 n]: {step_size, bias2_sqrt} of tensor i at [2 i], read instead of the arrays above
-};
-
-__global__ __launch_bounds__(64) void adam_multi_kernel(AdamMultiArgs a) {
-  float* theta = nullptr;
-  const float* grad = nullptr;
-  float *m = nullptr, *v = nullptr;
-  int size = 0;
-  AdamArgs s{};
-  s.beta1 = a.beta1, s.beta2 = a.beta2, s.one_minus_beta1 = a.one_minus_beta1, s.one_minus_beta2 = a.one_minus_beta2, s.eps = a.eps;
-  // (compile-time indices: indexing the by-value argument arrays with blockIdx would send them through scratch memory)
-#pragma unroll
-  for (int i = 0; i < ADAM_MULTI_MAX; ++i)
-    if ((int)blockIdx.x == i) {
-      theta = a.theta[i], grad = a.grad[i], m = a.m[i], v = a.v[i], size = a.size[i];
-      s.step_size = a.step_size[i], s.bias2_sqrt = a.bias2_sqrt[i];
-    }
-  if (a.bias_dev) s.step_size = a.bias_dev[2 * blockIdx.x], s.bias2_sqrt = a.bias_dev[2 * blockIdx.x + 1];
-  for (int j = threadIdx.x; j < size; j += 64) {
-    float th = theta[j], mj = m[j], vj = v[j];
-    adam_update(th, mj, vj, grad[j], s);
-    theta[j] = th, m[j] = mj, v[j] = vj;
-  }
-}
-
-extern "C" int jd_adam_step_multi(int n_tensors, float* const* theta, const float* const* grad, float* const* exp_avg,
-                                  float* const* exp_avg_sq, const int* sizes, const float* step_size,
-                                  const float* bias2_sqrt, float beta1, float beta2, float one_minus_beta1,
-                                  float one_minus_beta2, float eps, const float* bias_dev, void* stream) {
-  JD_REQUIRE(theta && grad && exp_avg && exp_avg_sq && sizes && (bias_dev || (step_size && bias2_sqrt)),
-             "jd_adam_step_multi: null argument");
-  JD_REQUIRE(n_tensors >= 1 && n_tensors <= ADAM_MULTI_MAX, "jd_adam_step_multi: n_tensors = %d not in [1, %d]", n_tensors,
-             ADAM_MULTI_MAX);
-  AdamMultiArgs a{};
-  for (int i = 0; i < n_tensors; ++i) {
-    JD_REQUIRE(theta[i] && grad[i] && exp_avg[i] && exp_avg_sq[i] && sizes[i] > 0, "jd_adam_step_multi: null tensor %d", i);
-    a.theta[i] = theta[i], a.grad[i] = grad[i], a.m[i] = exp_avg[i], a.v[i] = exp_avg_sq[i], a.size[i] = sizes[i];
-    if (!bias_dev) a.step_size[i] = step_size[i], a.bias2_sqrt[i] = bias2_sqrt[i];
-  }
-  a.bias_dev = bias_dev;
-  a.beta1 = beta1, a.beta2 = beta2, a.one_minus_beta1 = one_minus_beta1, a.one_minus_beta2 = one_minus_beta2, a.eps = eps;
-  ProfScope prof(JD_KERNEL_ADAM, as_stream(stream));
-  adam_multi_kernel<<<n_tensors, 64, 0, as_stream(stream)>>>(a);
-  JD_LAUNCH_CHECK();
-  return JD_OK;
-}
-
-extern "C" int jd_sgd_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
-                           const float* mask, size_t n, float lr, int zero_grad, int use_log_flux, void* stream) {
-  JD_REQUIRE(theta && flux_in && flux_out && grad_flux && n > 0, "jd_sgd_step: null argument or n == 0");
-  AdamArgs a{theta, flux_in, flux_out, grad_flux, nullptr, nullptr, mask, n,
-             0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, lr, zero_grad, 1, use_log_flux ? 0 : 1, nullptr};
-  return launch_adam(a, as_stream(stream));
 }
 
 extern "C" int jd_version(void) { return 100; }

@@ -79,7 +79,7 @@ struct GmmGatherArgs {
   // their un-rolled column is a multiple of 4 and the gradient image is read and written with 16-byte accesses
   int vec;
   // fused optimizer step (do_step; tile kernel, whole image): instead of grad += coef * sum the kernel forms
-  // g = step.grad_flux[pixel] + coef * sum (the other gradient terms, read only) and applies the update of adam_kernel to
+  // g = step.grad_flux[pixel] + coef * sum (the other gradient terms, read only) and applies the stand-alone step's update to
   // the pixel -- one pass less over the gradient image and one launch less per step
   int do_step;
   int preload;  // do_step: the step's streams are loaded before the patch rows (JD_GMM_GATHER_PRELOAD=0: behind the barrier)

@@ -1,5 +1,5 @@
-// The optimizer update of one pixel, shared by the stand-alone kernel (elementwise.hip: adam_kernel) and by the gather
-// kernel of the GMM prior that applies it in its epilogue (gmm_gather.hip): ONE device function, so both produce the same bits.
+// The optimizer update of one pixel, shared by the stand-alone kernels (optimizer.hip) and by the kernels of the GMM prior
+// that apply it in their epilogue (gmm_gather.hip: the gather, the band sum): ONE device function, so all produce the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,10 +34,8 @@ __device__ __forceinline__ void use_device_bias(AdamArgs& a) {
 
 __device__ inline void adam_update(float& th, float& m, float& v, float g, const AdamArgs& a) {
   // every product and sum rounded on its own: whether the compiler fuses a multiply-add depends on the kernel around it
-  // (adam_multi_kernel came out one ulp from adam_kernel), and every kernel that steps a parameter must give the same bits
-#ifndef JD_ADAM_CONTRACT  // (A/B only: -DJD_ADAM_CONTRACT leaves the fusing to the compiler)
+  // (the many-vector kernel came out one ulp from the image kernel), and every kernel that steps a parameter must give the same bits
 #pragma clang fp contract(off)
-#endif
   if (a.sgd) {
     // param.add_(grad, alpha=-lr) of torch.optim.SGD is ONE fused multiply-add (its float32 CPU kernel, bit for bit): the
     // bits of torch, and where the update nearly cancels the parameter a quarter of the error of a product rounded on its

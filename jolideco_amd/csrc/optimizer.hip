@@ -1,12 +1,14 @@
-// The optimizer step WITH the options of torch.optim.Adam / torch.optim.SGD (gfx950): weight decay, decoupled weight decay,
-// AMSGrad; weight decay, momentum, dampening, Nesterov.  A streaming kernel family of its own, built the way adam_kernel
-// (elementwise.hip) is -- chain rule, update, new flux in one pass, 16 B per lane where every image is 16-byte aligned, a
-// scalar kernel otherwise, the bias terms by value or from device memory.  jd_adam.h and the kernels that end in it
-// (adam_kernel, adam_multi_kernel, the tiled gather, the band sum) know no option and stay as they are; with every option
-// off the update here IS adam_update, the same bits; with one, Adam's few operations per parameter run in double
-// (adam_update_wide below) and SGD's in torch's own float32 order.
-// Bytes per pixel (log flux, no mask): Adam 36 (theta, flux, grad, m, v in; theta, flux, m, v out), + amsgrad 44;
-// SGD 20, + momentum 28 (first step 24: the buffer is only written).
+// The stand-alone optimizer step (gfx950): every kernel that steps a parameter outside a prior's own last kernel, and the six
+// C entries that launch them.  Chain rule, update and new flux in one pass, 16 B per lane where every image is 16-byte
+// aligned, a scalar kernel otherwise, the bias terms by value or from device memory.  Two kernels, one launcher each:
+// optimizer_kernel (an image; jd_adam_step, jd_adam_step_addends, jd_sgd_step, jd_optimizer_step) and
+// optimizer_multi_kernel (up to 64 small vectors; jd_adam_step_multi, jd_optimizer_step_multi).  The KIND of an
+// instantiation says what is compiled in: the plain kinds are adam_update (jd_adam.h) in float32 and nothing else -- the
+// bits of the fused steps of gmm_gather.hip -- and the options of torch.optim.Adam / torch.optim.SGD (weight decay,
+// decoupled weight decay, AMSGrad; weight decay, momentum, dampening, Nesterov) are kinds of their own: Adam's few
+// operations per parameter in double (adam_update_wide below), SGD's in torch's own float32 order.
+// Bytes per pixel (log flux, no mask): Adam 36 (theta, flux, grad, m, v in; theta, flux, m, v out), + 4 per addend image,
+// + amsgrad 44; SGD 20, + momentum 28 (first step 24: the buffer is only written).
 #include <cmath>
 #include <cstdint>
 
@@ -17,9 +19,13 @@
 namespace jd {
 
 constexpr int OPT_BLOCK = 256;
-constexpr int OPT_MAX_BLOCKS = 4096;  // grid cap of the grid-stride loops (as adam_kernel)
-// what a kernel instantiation keeps in registers beside theta: the state images it reads and writes
-enum { OPT_ADAM = 0, OPT_AMSGRAD = 1, OPT_SGD = 2, OPT_MOMENTUM = 3 };
+constexpr int OPT_MAX_BLOCKS = 4096;  // grid cap of the grid-stride loops
+// what a kernel instantiation compiles in: the update (float32 adam_update for OPT_ADAM and OPT_SGD, double for
+// OPT_ADAM_DECAY and OPT_AMSGRAD -- the plain kinds hold no double arithmetic and no register for it) and the state images
+// it keeps in registers beside theta
+enum { OPT_ADAM = 0, OPT_ADAM_DECAY = 1, OPT_AMSGRAD = 2, OPT_SGD = 3, OPT_MOMENTUM = 4 };
+constexpr bool opt_moments(int kind) { return kind == OPT_ADAM || kind == OPT_ADAM_DECAY || kind == OPT_AMSGRAD; }
+constexpr bool opt_third(int kind) { return kind == OPT_AMSGRAD || kind == OPT_MOMENTUM; }
 
 struct OptTerms {  // uniform terms of the options (the Adam terms of the plain update travel in AdamArgs)
   float weight_decay;         // 0: none
@@ -30,7 +36,7 @@ struct OptTerms {  // uniform terms of the options (the Adam terms of the plain 
 };
 
 struct OptArgs {
-  AdamArgs a;   // images, n, the terms of the plain update, zero_grad, sgd, linear, bias_dev (addend unused)
+  AdamArgs a;   // images, n, the terms of the plain update, zero_grad, sgd, linear, bias_dev, addend (OPT_ADAM only)
   float* s;     // OPT_AMSGRAD: max_exp_avg_sq; OPT_MOMENTUM: momentum_buffer
   OptTerms t;
   int first_step;
@@ -68,21 +74,20 @@ __device__ __forceinline__ void adam_update_wide(float& th, float& m, float& v, 
 }
 
 // One parameter: th, the moments m / v and the third state s (max_exp_avg_sq or the momentum buffer) are updated in place.
-// With no option active this IS adam_update (jd_adam.h): the bits of jd_adam_step / jd_sgd_step and of the fused kernels.
+// OPT_ADAM, and OPT_SGD without weight decay, ARE adam_update (jd_adam.h): the bits of the fused kernels.
 // SGD with options follows torch's float32 CPU kernels operation by operation -- add(x, alpha=c) is one multiply-add, as
 // jd_adam.h found for the plain step -- and gives their bits; explicit fmaf and `fp contract(off)` keep every path the same
-// in every kernel: jd_optimizer_step_multi must give the bits of jd_optimizer_step.
+// in every kernel: optimizer_multi_kernel must give the bits of optimizer_kernel.
 template <int KIND>
 __device__ __forceinline__ void opt_update(float& th, float& m, float& v, float& s, float g, const AdamArgs& a,
                                            const OptTerms& t, int first_step) {
 #pragma clang fp contract(off)
   if constexpr (KIND == OPT_AMSGRAD) {
     adam_update_wide<true>(th, m, v, s, g, a, t);
+  } else if constexpr (KIND == OPT_ADAM_DECAY) {
+    adam_update_wide<false>(th, m, v, s, g, a, t);
   } else if constexpr (KIND == OPT_ADAM) {
-    if (t.weight_decay != 0.f)
-      adam_update_wide<false>(th, m, v, s, g, a, t);
-    else
-      adam_update(th, m, v, g, a);  // (no option active)
+    adam_update(th, m, v, g, a);
   } else {
     if (t.weight_decay != 0.f) g = fmaf(t.weight_decay, th, g);  // grad.add(param, alpha=weight_decay)
     if constexpr (KIND == OPT_SGD) {
@@ -96,7 +101,7 @@ __device__ __forceinline__ void opt_update(float& th, float& m, float& v, float&
   }
 }
 
-// chain rule + update + new flux of one pixel, as adam_pixel
+// chain rule + update + new flux of one pixel: adam_pixel (jd_adam.h, the fused kernels' form) with the third state image
 template <int KIND>
 __device__ __forceinline__ void opt_pixel(float& th, float& f, float& m, float& v, float& s, float gf, float mk,
                                           const OptArgs& o) {
@@ -109,10 +114,11 @@ __device__ __forceinline__ void opt_pixel(float& th, float& f, float& m, float& 
 
 __device__ __forceinline__ void unpack(const float4 q, float (&x)[4]) { x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w; }
 
-template <int VEC, int KIND>
+// NA: addend images (a.addend[0 .. NA) are set), added to the gradient in order before the update (jd_adam.h)
+template <int VEC, int KIND, int NA>
 __global__ __launch_bounds__(OPT_BLOCK) void optimizer_kernel(OptArgs o) {
-  constexpr bool MOMENTS = KIND == OPT_ADAM || KIND == OPT_AMSGRAD;
-  constexpr bool THIRD = KIND == OPT_AMSGRAD || KIND == OPT_MOMENTUM;
+  static_assert(NA == 0 || KIND == OPT_ADAM, "only the plain Adam step takes addend images (jd_adam_step_addends)");
+  constexpr bool MOMENTS = opt_moments(KIND), THIRD = opt_third(KIND);
   use_device_bias(o.a);
   const AdamArgs& a = o.a;
   // (the first step of a momentum buffer writes it without reading it)
@@ -126,6 +132,9 @@ __global__ __launch_bounds__(OPT_BLOCK) void optimizer_kernel(OptArgs o) {
       unpack(*reinterpret_cast<const float4*>(a.theta + i), th);
       unpack(*reinterpret_cast<const float4*>(a.flux_in + i), f);
       unpack(*reinterpret_cast<const float4*>(a.grad_flux + i), gf);
+      float4 a4[NA ? NA : 1];
+#pragma unroll
+      for (int k = 0; k < NA; ++k) a4[k] = *reinterpret_cast<const float4*>(a.addend[k] + i);
       if constexpr (MOMENTS) {
         unpack(*reinterpret_cast<const float4*>(a.m + i), m);
         unpack(*reinterpret_cast<const float4*>(a.v + i), v);
@@ -133,8 +142,12 @@ __global__ __launch_bounds__(OPT_BLOCK) void optimizer_kernel(OptArgs o) {
       if constexpr (THIRD)
         if (read_third) unpack(*reinterpret_cast<const float4*>(o.s + i), s);
       if (a.mask) unpack(*reinterpret_cast<const float4*>(a.mask + i), mk);
+#pragma unroll
+      for (int k = 0; k < NA; ++k) gf[0] += a4[k].x, gf[1] += a4[k].y, gf[2] += a4[k].z, gf[3] += a4[k].w;
     } else {
       th[0] = a.theta[i], f[0] = a.flux_in[i], gf[0] = a.grad_flux[i];
+#pragma unroll
+      for (int k = 0; k < NA; ++k) gf[0] += a.addend[k][i];
       if constexpr (MOMENTS) m[0] = a.m[i], v[0] = a.v[i];
       if constexpr (THIRD)
         if (read_third) s[0] = o.s[i];
@@ -160,8 +173,10 @@ __global__ __launch_bounds__(OPT_BLOCK) void optimizer_kernel(OptArgs o) {
   }
 }
 
-// MANY small parameter vectors in one launch, as adam_multi_kernel: one block per tensor, the update of
-// optimizer_kernel with use_log_flux = 0 and no mask (opt_update: the same device function, the same bits).
+// MANY small parameter vectors in one launch (the calibration parameters of the datasets of a joint step: two tensors of 2
+// and 1 floats per dataset -- one launch each took 4.5 us, sixteen per step of eight observations; the source vectors of a
+// sparse component).  One block per tensor, the update of optimizer_kernel with use_log_flux = 0 and no mask (opt_update:
+// the same device function, the same bits).
 constexpr int OPT_MULTI_MAX = 64;
 struct OptMultiArgs {  // (3.4 KB of the 4 KB a kernel's arguments may take)
   float* theta[OPT_MULTI_MAX];
@@ -179,8 +194,7 @@ struct OptMultiArgs {  // (3.4 KB of the 4 KB a kernel's arguments may take)
 
 template <int KIND>
 __global__ __launch_bounds__(64) void optimizer_multi_kernel(OptMultiArgs a) {
-  constexpr bool MOMENTS = KIND == OPT_ADAM || KIND == OPT_AMSGRAD;
-  constexpr bool THIRD = KIND == OPT_AMSGRAD || KIND == OPT_MOMENTUM;
+  constexpr bool MOMENTS = opt_moments(KIND), THIRD = opt_third(KIND);
   float* theta = nullptr;
   const float* grad = nullptr;
   float *m = nullptr, *v = nullptr, *s = nullptr;
@@ -232,8 +246,11 @@ static int read_options(const jd_optimizer_options* opt, const char* who, int& k
     JD_REQUIRE(!opt->nesterov || (opt->momentum > 0.0 && opt->dampening == 0.0),
                "%s: nesterov needs a momentum and zero dampening", who);
   }
-  kind = adam ? (opt->amsgrad ? OPT_AMSGRAD : OPT_ADAM) : (opt->momentum != 0.0 ? OPT_MOMENTUM : OPT_SGD);
   t.weight_decay = (float)opt->weight_decay;
+  if (adam)
+    kind = opt->amsgrad ? OPT_AMSGRAD : (t.weight_decay != 0.f ? OPT_ADAM_DECAY : OPT_ADAM);
+  else
+    kind = opt->momentum != 0.0 ? OPT_MOMENTUM : OPT_SGD;
   t.decoupled = opt->decoupled_weight_decay ? 1 : 0;
   t.decay = (float)(1.0 - opt->lr * opt->weight_decay);
   t.momentum = (float)opt->momentum;
@@ -242,12 +259,60 @@ static int read_options(const jd_optimizer_options* opt, const char* who, int& k
   return JD_OK;
 }
 
-template <int KIND>
+template <int KIND, int NA = 0>
 static void launch_optimizer_kernel(bool vec, unsigned blocks, const OptArgs& o, hipStream_t stream) {
   if (vec)
-    optimizer_kernel<4, KIND><<<blocks, OPT_BLOCK, 0, stream>>>(o);
+    optimizer_kernel<4, KIND, NA><<<blocks, OPT_BLOCK, 0, stream>>>(o);
   else
-    optimizer_kernel<1, KIND><<<blocks, OPT_BLOCK, 0, stream>>>(o);
+    optimizer_kernel<1, KIND, NA><<<blocks, OPT_BLOCK, 0, stream>>>(o);
+}
+
+// The launcher of every stand-alone step of an image: `o` is filled (o.s and the state images a kind does not use are null).
+static int launch_step(int kind, const OptArgs& o, hipStream_t stream) {
+  const AdamArgs& a = o.a;
+  int na = 0;
+  while (na < ADDEND_MAX && a.addend[na]) ++na;
+  // float4 accesses: every image the kernel touches is 16-byte aligned (null images count as aligned), else pixel by pixel
+  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
+  bool vec = (a.n % 4 == 0) && aligned(a.theta) && aligned(a.flux_in) && aligned(a.flux_out) && aligned(a.grad_flux) &&
+             aligned(a.m) && aligned(a.v) && aligned(o.s) && aligned(a.mask);
+  for (int k = 0; k < na; ++k) vec = vec && aligned(a.addend[k]);
+  const size_t per_block = (size_t)OPT_BLOCK * (vec ? 4 : 1);
+  size_t count = (a.n + per_block - 1) / per_block;
+  if (count > OPT_MAX_BLOCKS) count = OPT_MAX_BLOCKS;
+  const unsigned blocks = (unsigned)count;
+  ProfScope prof(JD_KERNEL_ADAM, stream);
+  switch (kind) {
+    case OPT_ADAM:
+      switch (na) {
+        case 0: launch_optimizer_kernel<OPT_ADAM, 0>(vec, blocks, o, stream); break;
+        case 1: launch_optimizer_kernel<OPT_ADAM, 1>(vec, blocks, o, stream); break;
+        case 2: launch_optimizer_kernel<OPT_ADAM, 2>(vec, blocks, o, stream); break;
+        case 3: launch_optimizer_kernel<OPT_ADAM, 3>(vec, blocks, o, stream); break;
+        default: launch_optimizer_kernel<OPT_ADAM, 4>(vec, blocks, o, stream); break;
+      }
+      break;
+    case OPT_ADAM_DECAY: launch_optimizer_kernel<OPT_ADAM_DECAY>(vec, blocks, o, stream); break;
+    case OPT_AMSGRAD: launch_optimizer_kernel<OPT_AMSGRAD>(vec, blocks, o, stream); break;
+    case OPT_SGD: launch_optimizer_kernel<OPT_SGD>(vec, blocks, o, stream); break;
+    default: launch_optimizer_kernel<OPT_MOMENTUM>(vec, blocks, o, stream); break;
+  }
+  JD_LAUNCH_CHECK();
+  return JD_OK;
+}
+
+// The launcher of every step of many small vectors: one block per tensor.
+static int launch_step_multi(int kind, int n_tensors, const OptMultiArgs& a, hipStream_t stream) {
+  ProfScope prof(JD_KERNEL_ADAM, stream);
+  switch (kind) {
+    case OPT_ADAM: optimizer_multi_kernel<OPT_ADAM><<<n_tensors, 64, 0, stream>>>(a); break;
+    case OPT_ADAM_DECAY: optimizer_multi_kernel<OPT_ADAM_DECAY><<<n_tensors, 64, 0, stream>>>(a); break;
+    case OPT_AMSGRAD: optimizer_multi_kernel<OPT_AMSGRAD><<<n_tensors, 64, 0, stream>>>(a); break;
+    case OPT_SGD: optimizer_multi_kernel<OPT_SGD><<<n_tensors, 64, 0, stream>>>(a); break;
+    default: optimizer_multi_kernel<OPT_MOMENTUM><<<n_tensors, 64, 0, stream>>>(a); break;
+  }
+  JD_LAUNCH_CHECK();
+  return JD_OK;
 }
 
 }  // namespace jd
@@ -262,7 +327,7 @@ extern "C" int jd_optimizer_step(float* theta, const float* flux_in, float* flux
   int kind = 0;
   OptArgs o{};
   if (int status = read_options(options, "jd_optimizer_step", kind, o.t)) return status;
-  const bool adam = kind == OPT_ADAM || kind == OPT_AMSGRAD;
+  const bool adam = opt_moments(kind);
   JD_REQUIRE(!adam || (exp_avg && exp_avg_sq), "jd_optimizer_step: Adam needs its moment images");
   JD_REQUIRE(kind != OPT_AMSGRAD || max_exp_avg_sq, "jd_optimizer_step: amsgrad needs max_exp_avg_sq");
   JD_REQUIRE(kind != OPT_MOMENTUM || momentum_buffer, "jd_optimizer_step: momentum needs momentum_buffer");
@@ -279,23 +344,42 @@ extern "C" int jd_optimizer_step(float* theta, const float* flux_in, float* flux
   }
   o.s = kind == OPT_AMSGRAD ? max_exp_avg_sq : (kind == OPT_MOMENTUM ? momentum_buffer : nullptr);
   o.first_step = (kind == OPT_MOMENTUM && options->first_step) ? 1 : 0;
-  // float4 accesses: every image the kernel touches is 16-byte aligned (null images count as aligned), else pixel by pixel
-  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
-  const bool vec = (n % 4 == 0) && aligned(theta) && aligned(flux_in) && aligned(flux_out) && aligned(grad_flux) &&
-                   aligned(a.m) && aligned(a.v) && aligned(o.s) && aligned(mask);
-  const size_t per_block = (size_t)OPT_BLOCK * (vec ? 4 : 1);
-  size_t blocks = (n + per_block - 1) / per_block;
-  if (blocks > OPT_MAX_BLOCKS) blocks = OPT_MAX_BLOCKS;
-  hipStream_t s = as_stream(stream);
-  ProfScope prof(JD_KERNEL_ADAM, s);
-  switch (kind) {
-    case OPT_ADAM: launch_optimizer_kernel<OPT_ADAM>(vec, (unsigned)blocks, o, s); break;
-    case OPT_AMSGRAD: launch_optimizer_kernel<OPT_AMSGRAD>(vec, (unsigned)blocks, o, s); break;
-    case OPT_SGD: launch_optimizer_kernel<OPT_SGD>(vec, (unsigned)blocks, o, s); break;
-    default: launch_optimizer_kernel<OPT_MOMENTUM>(vec, (unsigned)blocks, o, s); break;
-  }
-  JD_LAUNCH_CHECK();
-  return JD_OK;
+  return launch_step(kind, o, as_stream(stream));
+}
+
+extern "C" int jd_adam_step_addends(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
+                                    float* exp_avg, float* exp_avg_sq, const float* mask, size_t n, float step_size,
+                                    float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
+                                    float bias2_sqrt, float eps, int zero_grad, int use_log_flux, const float* bias_dev,
+                                    const float* const* addends, void* stream) {
+  JD_REQUIRE(theta && flux_in && flux_out && grad_flux && exp_avg && exp_avg_sq && n > 0,
+             "jd_adam_step: null argument or n == 0");
+  OptArgs o{};
+  o.a = AdamArgs{theta, flux_in, flux_out, grad_flux, exp_avg, exp_avg_sq, mask, n,
+                 step_size, beta1, beta2, one_minus_beta1, one_minus_beta2, bias2_sqrt, eps, 0.f, zero_grad, 0,
+                 use_log_flux ? 0 : 1, bias_dev};
+  static_assert(ADDEND_MAX == JD_ADDEND_MAX, "the host array of jd_adam_step_addends and AdamArgs::addend");
+  for (int k = 0; addends && k < ADDEND_MAX && addends[k]; ++k) o.a.addend[k] = addends[k];  // (the leading non-null entries)
+  return launch_step(OPT_ADAM, o, as_stream(stream));
+}
+
+extern "C" int jd_adam_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
+                            float* exp_avg, float* exp_avg_sq, const float* mask, size_t n, float step_size,
+                            float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
+                            float bias2_sqrt, float eps, int zero_grad, int use_log_flux, const float* bias_dev,
+                            void* stream) {
+  return jd_adam_step_addends(theta, flux_in, flux_out, grad_flux, exp_avg, exp_avg_sq, mask, n, step_size, beta1, beta2,
+                              one_minus_beta1, one_minus_beta2, bias2_sqrt, eps, zero_grad, use_log_flux, bias_dev, nullptr,
+                              stream);
+}
+
+extern "C" int jd_sgd_step(float* theta, const float* flux_in, float* flux_out, float* grad_flux,
+                           const float* mask, size_t n, float lr, int zero_grad, int use_log_flux, void* stream) {
+  JD_REQUIRE(theta && flux_in && flux_out && grad_flux && n > 0, "jd_sgd_step: null argument or n == 0");
+  OptArgs o{};
+  o.a = AdamArgs{theta, flux_in, flux_out, grad_flux, nullptr, nullptr, mask, n,
+                 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, lr, zero_grad, 1, use_log_flux ? 0 : 1, nullptr};
+  return launch_step(OPT_SGD, o, as_stream(stream));
 }
 
 extern "C" int jd_optimizer_step_multi(int n_tensors, float* const* theta, const float* const* grad, float* const* exp_avg,
@@ -309,7 +393,7 @@ extern "C" int jd_optimizer_step_multi(int n_tensors, float* const* theta, const
   int kind = 0;
   OptMultiArgs a{};
   if (int status = read_options(options, "jd_optimizer_step_multi", kind, a.t)) return status;
-  const bool adam = kind == OPT_ADAM || kind == OPT_AMSGRAD;
+  const bool adam = opt_moments(kind);
   JD_REQUIRE(!adam || (exp_avg && exp_avg_sq && (bias_dev || (step_size && bias2_sqrt))),
              "jd_optimizer_step_multi: Adam needs its moments and bias terms");
   JD_REQUIRE(kind != OPT_AMSGRAD || max_exp_avg_sq, "jd_optimizer_step_multi: amsgrad needs max_exp_avg_sq");
@@ -330,14 +414,24 @@ extern "C" int jd_optimizer_step_multi(int n_tensors, float* const* theta, const
   } else {
     a.lr = (float)options->lr;
   }
-  hipStream_t s = as_stream(stream);
-  ProfScope prof(JD_KERNEL_ADAM, s);
-  switch (kind) {
-    case OPT_ADAM: optimizer_multi_kernel<OPT_ADAM><<<n_tensors, 64, 0, s>>>(a); break;
-    case OPT_AMSGRAD: optimizer_multi_kernel<OPT_AMSGRAD><<<n_tensors, 64, 0, s>>>(a); break;
-    case OPT_SGD: optimizer_multi_kernel<OPT_SGD><<<n_tensors, 64, 0, s>>>(a); break;
-    default: optimizer_multi_kernel<OPT_MOMENTUM><<<n_tensors, 64, 0, s>>>(a); break;
+  return launch_step_multi(kind, n_tensors, a, as_stream(stream));
+}
+
+extern "C" int jd_adam_step_multi(int n_tensors, float* const* theta, const float* const* grad, float* const* exp_avg,
+                                  float* const* exp_avg_sq, const int* sizes, const float* step_size,
+                                  const float* bias2_sqrt, float beta1, float beta2, float one_minus_beta1,
+                                  float one_minus_beta2, float eps, const float* bias_dev, void* stream) {
+  JD_REQUIRE(theta && grad && exp_avg && exp_avg_sq && sizes && (bias_dev || (step_size && bias2_sqrt)),
+             "jd_adam_step_multi: null argument");
+  JD_REQUIRE(n_tensors >= 1 && n_tensors <= OPT_MULTI_MAX, "jd_adam_step_multi: n_tensors = %d not in [1, %d]", n_tensors,
+             OPT_MULTI_MAX);
+  OptMultiArgs a{};
+  for (int i = 0; i < n_tensors; ++i) {
+    JD_REQUIRE(theta[i] && grad[i] && exp_avg[i] && exp_avg_sq[i] && sizes[i] > 0, "jd_adam_step_multi: null tensor %d", i);
+    a.theta[i] = theta[i], a.grad[i] = grad[i], a.m[i] = exp_avg[i], a.v[i] = exp_avg_sq[i], a.size[i] = sizes[i];
+    if (!bias_dev) a.step_size[i] = step_size[i], a.bias2_sqrt[i] = bias2_sqrt[i];
   }
-  JD_LAUNCH_CHECK();
-  return JD_OK;
+  a.bias_dev = bias_dev;
+  a.beta1 = beta1, a.beta2 = beta2, a.one_minus_beta1 = one_minus_beta1, a.one_minus_beta2 = one_minus_beta2, a.eps = eps;
+  return launch_step_multi(OPT_ADAM, n_tensors, a, as_stream(stream));
 }

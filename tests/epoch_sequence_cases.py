@@ -313,14 +313,16 @@ def build_session(core, case):
 
 @contextlib.contextmanager
 def recording_library(core, rec):
-    """The module-level calls of the epoch body -- the Adam launch of the small parameters, `jd_sgd_step` of the library,
-    the band sums of `ops` -- replaced by recorders, and put back."""
+    """The module-level calls of the epoch body -- the step of the small parameters, the band sums of `ops` -- replaced
+    by recorders, and put back.  The step of the small parameters is one launch for Adam and for SGD; its log keeps the
+    form of the recorded sequences: one entry with every stepped parameter for Adam, one entry per stepped parameter, in
+    order, for SGD."""
     from importlib import import_module
 
     ops = import_module(core.__name__.rsplit(".", 1)[0] + ".ops")
     names = rec.names
 
-    def adam_step_many(cfg, items, cache, bias_dev=None):
+    def step_parameters(cfg, items, cache, bias_dev=None):
         stepped = []
         for p, st in items:
             if p.grad is None:
@@ -329,13 +331,14 @@ def recording_library(core, rec):
                 continue
             st["step"] += 1
             stepped.append([names(p.data), st["step"]])
-        rec.log.append({"kind": "adam-step-many", "items": stepped, "bias_dev": bias_dev is not None})
+            if cfg.optimizer_type != "adam":
+                rec.log.append({"kind": "sgd-step", "param": names(p.data), "grad": names(p.grad), "n": p.numel(),
+                                "lr": cfg.optimizer_kwargs["lr"]})
+        if cfg.optimizer_type == "adam":
+            rec.log.append({"kind": "adam-step-many", "items": stepped, "bias_dev": bias_dev is not None})
 
-    class Library:
-        @staticmethod
-        def jd_sgd_step(theta, flux_in, flux_out, grad, mask, n, lr, zero, use_log_flux, stream):
-            rec.log.append({"kind": "sgd-step", "param": theta, "grad": grad, "n": n, "lr": lr})
-            return 0
+    class Library:  # (no entry: a library call the epoch body makes on its own fails the case)
+        pass
 
     def bands(grad, shifts, bands, chunk, y_ranges):
         rec.log.append({"kind": "add-rolled-bands", "grad": names(grad), "shifts": _plain(shifts), "bands": names(bands),
@@ -345,7 +348,7 @@ def recording_library(core, rec):
         rec.log.append({"kind": "add-rolled-bands+step", "shape": list(shape), "shifts": _plain(shifts), "bands": names(bands),
                         "chunk": chunk, "y_ranges": [list(r) for r in y_ranges], "step": rec.step_args(step)})
 
-    patches = [(core, "_adam_step_many", adam_step_many), (core, "ptr", names), (core, "stream_ptr", lambda device=None: None),
+    patches = [(core, "_step_parameters", step_parameters), (core, "ptr", names), (core, "stream_ptr", lambda device=None: None),
                (core, "check", lambda status: None), (core._hip, "lib", lambda: Library),
                (ops, "add_rolled_bands", bands), (ops, "add_rolled_bands_step", bands_step)]
     saved = [(module, name, getattr(module, name)) for module, name, _ in patches]

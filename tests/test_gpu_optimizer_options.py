@@ -273,21 +273,24 @@ def test_device_bias_terms_give_the_bits_of_the_by_value_call(n, linear, name):
 MULTI_SIZES = [1, 2, 3, 64, 65, 200]
 
 
+# no option set: what a session's small parameters take by default, held to the legacy single-tensor entries
+PLAIN_SETS = {"plain-adam": (False, {}), "plain-sgd": (True, {})}
 # (SGD has no bias terms)
 MULTI_CASES = [pytest.param(name, device_bias, id=f"{name}-{'bias_dev' if device_bias else 'by-value'}")
-               for name in SETS for device_bias in ((False, True) if name in ADAM_SETS else (False,))]
+               for name in SETS + sorted(PLAIN_SETS)
+               for device_bias in ((False, True) if name in ADAM_SETS + ["plain-adam"] else (False,))]
 
 
 @pytest.mark.parametrize("name,device_bias", MULTI_CASES)
 def test_optimizer_step_multi_gives_the_single_tensor_bits(name, device_bias):
     """jd_optimizer_step_multi on tensors of ragged sizes, each at a step count of its own and -- momentum -- some on their
     first step (buffer NaN: written, not read) and some on a later one, against one jd_optimizer_step (linear, no mask) per
-    tensor."""
+    tensor; with no option set against one jd_adam_step / jd_sgd_step per tensor."""
     from jolideco_amd import _hip
     from jolideco_amd._hip import check, ptr, ptr_array, stream_ptr
     from jolideco_amd.ops import adam_bias_terms
 
-    sgd, options = cases.OPTION_SETS[name]
+    sgd, options = PLAIN_SETS[name] if name in PLAIN_SETS else cases.OPTION_SETS[name]
     lr = cases.learning_rate(sgd, True, options)
     rs = np.random.RandomState(37)
     counts = [1 + i % 5 for i in range(len(MULTI_SIZES))]
@@ -309,10 +312,18 @@ def test_optimizer_step_multi_gives_the_single_tensor_bits(name, device_bias):
     singles = []
     for t, count, first in zip(tensors, counts, firsts):
         d = device(t)
-        args = options_struct(sgd, lr, options, count, first)
-        check(_hip.lib().jd_optimizer_step(ptr(d["theta"]), ptr(d["theta"]), ptr(d["theta"]), ptr(d["grad"]), ptr(d.get("m")), ptr(d.get("v")),
-                                           ptr(d.get("vmax")), ptr(d.get("buf")), None, d["theta"].numel(), ctypes.byref(args), 0, 0, None,
-                                           stream_ptr(DEV)))
+        theta, size = ptr(d["theta"]), d["theta"].numel()
+        if name == "plain-adam":
+            step_size, bias2_sqrt = adam_bias_terms(count, lr, *cases.BETAS)
+            beta1, beta2 = cases.BETAS
+            check(_hip.lib().jd_adam_step(theta, theta, theta, ptr(d["grad"]), ptr(d["m"]), ptr(d["v"]), None, size, step_size, beta1,
+                                          beta2, 1 - beta1, 1 - beta2, bias2_sqrt, cases.EPS, 0, 0, None, stream_ptr(DEV)))
+        elif name == "plain-sgd":
+            check(_hip.lib().jd_sgd_step(theta, theta, theta, ptr(d["grad"]), None, size, lr, 0, 0, stream_ptr(DEV)))
+        else:
+            args = options_struct(sgd, lr, options, count, first)
+            check(_hip.lib().jd_optimizer_step(theta, theta, theta, ptr(d["grad"]), ptr(d.get("m")), ptr(d.get("v")), ptr(d.get("vmax")),
+                                               ptr(d.get("buf")), None, size, ctypes.byref(args), 0, 0, None, stream_ptr(DEV)))
         singles.append(d)
     many = [device(t) for t in tensors]
     n = len(many)
@@ -333,6 +344,46 @@ def test_optimizer_step_multi_gives_the_single_tensor_bits(name, device_bias):
         assert not torch.equal(got["theta"], held(tensors[i]["theta"]))
 
 
+@pytest.mark.parametrize("optimizer_type", ["sgd", "adam"])
+def test_step_parameters_gives_the_single_tensor_bits_and_skips_a_parameter_without_gradient(optimizer_type):
+    """`core._step_parameters`, the step of a session's small parameters (one jd_optimizer_step_multi launch), on tensors of
+    2, 1 and 5 floats of which the middle one has no gradient, twice: the stepped tensors carry the bits of one jd_sgd_step /
+    jd_adam_step each, the parameter without gradient and its count are untouched, every other count advances by one."""
+    from jolideco_amd import _hip, core
+    from jolideco_amd._hip import check, ptr, stream_ptr
+    from jolideco_amd.ops import adam_bias_terms
+
+    cfg = core.MAPDeconvolver(device=DEV, optimizer_type=optimizer_type, display_progress=False)
+    lr, (beta1, beta2) = cfg.optimizer_kwargs["lr"], cases.BETAS
+    rs = np.random.RandomState(41)
+    start = [rs.normal(size=n).astype(np.float32) for n in (2, 1, 5)]
+    params = [torch.nn.Parameter(held(x)) for x in start]
+    for p in (params[0], params[2]):
+        p.grad = held(rs.normal(size=p.numel()).astype(np.float32))
+    stepper = core._CalibrationStepper(params, cfg)
+    want = [{"theta": held(x), "m": torch.zeros(x.size, device=DEV), "v": torch.zeros(x.size, device=DEV)} for x in start]
+    cache = {}
+    for count in (1, 2):
+        core._step_parameters(cfg, list(zip(stepper.params, stepper.state)), cache)
+        for i in (0, 2):
+            w, n = want[i], start[i].size
+            theta = ptr(w["theta"])
+            if optimizer_type == "sgd":
+                check(_hip.lib().jd_sgd_step(theta, theta, theta, ptr(params[i].grad), None, n, lr, 0, 0, stream_ptr(DEV)))
+            else:
+                step_size, bias2_sqrt = adam_bias_terms(count, lr, beta1, beta2)
+                check(_hip.lib().jd_adam_step(theta, theta, theta, ptr(params[i].grad), ptr(w["m"]), ptr(w["v"]), None, n, step_size,
+                                              beta1, beta2, 1 - beta1, 1 - beta2, bias2_sqrt, cases.EPS, 0, 0, None, stream_ptr(DEV)))
+        torch.cuda.synchronize()
+        assert [st["step"] for st in stepper.state] == [count, 0, count]
+        for i, (p, st, w) in enumerate(zip(params, stepper.state, want)):
+            assert bool(torch.isfinite(w["theta"]).all())
+            assert torch.equal(p.data, w["theta"]), f"call {count}, tensor {i}: theta"
+            assert torch.equal(st["exp_avg"], w["m"]) and torch.equal(st["exp_avg_sq"], w["v"]), f"call {count}, tensor {i}: moments"
+        assert torch.equal(params[1].data, held(start[1])) and not torch.equal(params[0].data, held(start[0]))
+    assert len(cache) == 1  # (the pointer arrays of the second call are those of the first)
+
+
 PLAIN_MODES = {"adam-log": (False, False), "adam-linear": (False, True), "sgd-log": (True, False), "sgd-linear": (True, True)}
 
 
@@ -342,7 +393,10 @@ PLAIN_MODES = {"adam-log": (False, False), "adam-linear": (False, True), "sgd-lo
 @pytest.mark.parametrize("n", B_SIZES)
 def test_every_option_off_gives_the_bits_of_the_plain_step(n, mode, masked, keys):
     """jd_optimizer_step with no option set -- and with the state images of the options present all the same -- against
-    jd_adam_step / jd_sgd_step on the trajectories of tests/optimizer_cases.py."""
+    jd_adam_step / jd_sgd_step on the trajectories of tests/optimizer_cases.py.  All three entries end in one launcher and
+    one kernel (csrc/optimizer.hip): what this holds is that the legacy wrappers and jd_optimizer_step translate their
+    arguments to the same launch.  The independent anchors of that kernel's bits are the fused steps of the gather and the
+    band-sum kernel (tests/test_gpu_kernels.py) and the float64 / torch-bit checks of tests/test_gpu_optimizer_step.py."""
     from jolideco_amd import _hip
     from jolideco_amd._hip import check, ptr, stream_ptr
     from jolideco_amd.ops import adam_bias_terms

@@ -5,7 +5,7 @@ Run by hand on the GPU box, one process, under a timeout:
 
 Step kernels at 2048^2, log flux, no mask -- streaming kernels bound by HBM, so the yardstick is bytes per pixel:
     adam            jd_adam_step                        36 B  (theta, flux, grad, m, v in; theta, flux, m, v out)
-    adam-off        jd_optimizer_step, no option        36 B  (the same arithmetic in the new kernel family)
+    adam-off        jd_optimizer_step, no option        36 B  (the same kernel through the other entry)
     adam-amsgrad    jd_optimizer_step, amsgrad          44 B  (+ max_exp_avg_sq in and out): 1.22 x adam by bytes
     sgd             jd_sgd_step                         20 B
     sgd-momentum    jd_optimizer_step, momentum 0.9     28 B  (+ momentum_buffer in and out): 1.40 x sgd by bytes
@@ -17,6 +17,10 @@ for every variant.
 --fit: also the headline fit of bench.py (2048^2, 8 observations, GMM prior K = 128, joint) with
 optimizer_kwargs={"amsgrad": True} beside the same fit under JOLIDECO_NO_FUSED_STEP=1, which has the same launch structure
 (prior into the gradient image, then a stand-alone step): iterations/s of both from this one process, alternating.
+--against PATH (repeatable): other builds of the library, e.g. a parent commit's (make -C jolideco_amd/csrc VARIANT=parent
+there, the .so copied beside the in-tree one) and a second copy of it under another name -- parent against parent is the
+spread.  jd_adam_step, jd_sgd_step, jd_adam_step_addends with 2 addends and jd_optimizer_step with amsgrad of every library:
+first one step on equal seeded images and `torch.equal` of what the plain entries wrote, then all of them timed alternating.
 """
 import argparse
 import ctypes
@@ -86,6 +90,98 @@ def step_variants(n, device):
     }
 
 
+AGAINST_ENTRIES = ("jd_adam_step", "jd_sgd_step", "jd_adam_step_addends", "jd_optimizer_step")
+AGAINST_PLAIN = ("adam", "sgd", "adam-addends2")  # (held to the other libraries' bits and time; adam-amsgrad is only reported)
+
+
+def load_library(path):
+    """The step entries of another build of the library (a parent commit's), with the argument types of `_hip.EXPORTS`."""
+    from jolideco_amd import _hip
+
+    handle = ctypes.CDLL(str(Path(path).resolve()))
+    for name in AGAINST_ENTRIES:
+        fn = getattr(handle, name)
+        fn.restype, fn.argtypes = _hip.EXPORTS[name]
+    return handle
+
+
+def against_variants(n, device, libs, seed=1):
+    """{entry: {library: (call, images)}} for jd_adam_step, jd_sgd_step, jd_adam_step_addends with 2 addends and
+    jd_optimizer_step with amsgrad, of every library in `libs` on images of its own drawn from the SAME seed per entry."""
+    from jolideco_amd import _hip
+    from jolideco_amd._hip import check, ptr, ptr_array, stream_ptr
+    from jolideco_amd.ops import adam_bias_terms
+
+    new = lambda a: torch.from_numpy(a.astype(np.float32)).to(device)  # noqa: E731
+    lr, beta1, beta2, eps = 1e-3, 0.9, 0.999, 1e-8
+    step_size, bias2_sqrt = adam_bias_terms(10, lr, beta1, beta2)
+    adam_terms = (step_size, beta1, beta2, 1 - beta1, 1 - beta2, bias2_sqrt, eps)
+    stream = stream_ptr(device)
+    amsgrad = _hip.OptimizerOptions(kind=_hip.OPTIMIZER_ADAM, step_size=step_size, beta1=beta1, beta2=beta2, one_minus_beta1=1 - beta1,
+                                    one_minus_beta2=1 - beta2, bias2_sqrt=bias2_sqrt, eps=eps, lr=lr, amsgrad=1)
+
+    def images(entry, entry_seed):
+        rs = np.random.RandomState(entry_seed)
+        theta = rs.normal(size=n)
+        im = {"theta": new(theta), "flux_in": new(np.exp(theta)), "flux_out": new(np.zeros(n)), "grad": new(rs.normal(size=n))}
+        if entry != "sgd":
+            im["exp_avg"], im["exp_avg_sq"] = new(0.1 * rs.normal(size=n)), new(rs.uniform(size=n) ** 2)
+        if entry == "adam-addends2":
+            im["addends"] = [new(rs.normal(size=n)), new(rs.normal(size=n))]
+            im["addend_array"] = ptr_array(im["addends"] + [None, None])  # (JD_ADDEND_MAX = 4 entries)
+        if entry == "adam-amsgrad":
+            im["max_exp_avg_sq"] = new(rs.uniform(size=n) ** 2)
+        return im
+
+    def call(entry, lib, im):
+        head = (ptr(im["theta"]), ptr(im["flux_in"]), ptr(im["flux_out"]), ptr(im["grad"]))
+        if entry == "sgd":
+            return lambda: check(lib.jd_sgd_step(*head, None, n, lr, 0, 1, stream))
+        moments = (ptr(im["exp_avg"]), ptr(im["exp_avg_sq"]))
+        if entry == "adam":
+            return lambda: check(lib.jd_adam_step(*head, *moments, None, n, *adam_terms, 0, 1, None, stream))
+        if entry == "adam-addends2":
+            return lambda: check(lib.jd_adam_step_addends(*head, *moments, None, n, *adam_terms, 0, 1, None, im["addend_array"], stream))
+        return lambda: check(lib.jd_optimizer_step(*head, *moments, ptr(im["max_exp_avg_sq"]), None, None, n, ctypes.byref(amsgrad), 0, 1,
+                                                   None, stream))
+
+    out = {}
+    for k, entry in enumerate(AGAINST_PLAIN + ("adam-amsgrad",)):
+        out[entry] = {}
+        for name, lib in libs.items():
+            im = images(entry, seed + k)
+            out[entry][name] = (call(entry, lib, im), im)
+    return out
+
+
+def run_against(paths, n, steps, warmup, repeats, device):
+    """The in-tree library ("child") against the libraries of `paths`: one step of every plain entry on equal images and
+    `torch.equal` of what it wrote, then the timing of `time_steps` over every (entry, library), alternating.  Per plain
+    entry: whether the child's median lies inside or below the band of round medians the other libraries span together."""
+    from jolideco_amd import _hip
+
+    libs = {"child": _hip.lib()}
+    libs.update({Path(p).stem.replace("libjolideco_hip_", ""): load_library(p) for p in paths})
+    variants = against_variants(n, device, libs)
+    bits = {}
+    for entry in AGAINST_PLAIN:
+        for call, _ in variants[entry].values():
+            call()
+        torch.cuda.synchronize(device)
+        child = variants[entry]["child"][1]
+        bits[entry] = {name: {key: bool(torch.equal(im[key], child[key])) for key in ("theta", "flux_out", "exp_avg", "exp_avg_sq") if key in im}
+                       for name, (_, im) in variants[entry].items() if name != "child"}
+    calls = {f"{entry}@{name}": call for entry, by_lib in variants.items() for name, (call, _) in by_lib.items()}
+    medians, spread = time_steps(calls, steps, warmup, repeats, device)
+    out = {"libraries": list(libs), "bits_equal": bits, "steps_us": medians, "steps_us_min_max": spread, "plain_entries": {}}
+    for entry in AGAINST_PLAIN:
+        others = [spread[f"{entry}@{name}"] for name in libs if name != "child"]
+        band = (min(lo for lo, _ in others), max(hi for _, hi in others))
+        child = medians[f"{entry}@child"]
+        out["plain_entries"][entry] = {"child_us": child, "band_us": band, "inside_or_below": child <= band[1]}
+    return out
+
+
 def time_steps(variants, steps, warmup, repeats, device):
     for _ in range(warmup):
         for call in variants.values():
@@ -139,6 +235,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--fit", action="store_true")
+    ap.add_argument("--against", action="append", default=[], metavar="PATH",
+                    help="another build of the library (repeatable): its step entries are held to the in-tree build's bits and time")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from jolideco_amd import _hip
@@ -153,6 +251,8 @@ def main():
               "momentum_over_sgd": medians["sgd-momentum"] / medians["sgd"], "momentum_over_sgd_by_bytes": 28 / 20,
               "off_over_adam": medians["adam-off"] / medians["adam"]}
     del keep
+    if args.against:
+        result["against"] = run_against(args.against, n, args.steps, args.warmup, args.repeats, device)
     if args.fit:
         result["fit"] = time_fits(device)
     line = json.dumps(result)
