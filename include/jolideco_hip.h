@@ -60,8 +60,8 @@ int jd_get_option(const char* key, int* is_set, int* value);
  * linear "same" convolution of an (H, W) image with a (kh, kw) kernel, zero outside the image; the
  * crop offset is the reference's `_centered` offset ((kh-1)/2, (kw-1)/2) (utils/torch.py:337-344).
  * Two methods compute the same function:
- *   FFT    where H is even, W % 4 == 0 and the padded lengths are of the form 2^a * {1, 3, 9} (<= 4608 columns, <= 2304 rows
- *          per image half): hand-written transforms on the un-padded grid (csrc/fftnative.hip: rows, columns with the
+ *   FFT    where the padded lengths are of the form 2^a * {1, 3, 9} (<= 9216 columns, <= 4608 rows per image half: images
+ *          up to 9216 columns x 9216 rows less the PSF's halo), an image half holds the PSF and W >= 8: hand-written transforms on the un-padded grid (csrc/fftnative.hip: rows, columns with the
  *          k-space product, rows^-1 with the epilogue; the likelihood step of a dataset in five launches, with
  *          up-sampling and calibration too); otherwise rocFFT R2C / k-space multiply / C2R on a zero padded (Hp, Wp)
  *          grid, Hp >= H+kh-1, Wp >= W+kw-1 rounded up to FFT-friendly (2,3,5-smooth, Wp % 4 == 0) sizes
@@ -76,7 +76,8 @@ int jd_get_option(const char* key, int* is_set, int* value);
  *          PSFs up to 68x68 (csrc/sepconv.hip).  Whether a PSF qualifies is decided by
  *          jd_psf_separable_rank() / jd_conv_psf_spectrum(); a PSF that does not is an error for such a plan.
  * JD_CONV_MODE_AUTO picks DIRECT when the PSF is small enough for it to be faster than FFT -- up to 17 taps; up to 33
- * where the native FFT sizes do not fit, on images below 2^20 pixels, or with option JD_DIRECT_AUTO_ALL --; it never picks
+ * where the native FFT sizes do not fit, on images below 2^20 pixels, or with option JD_DIRECT_AUTO_ALL (so a general PSF
+ * of 18 to 33 taps on an image of 4600 to 9216 columns or rows takes the native FFT plan, no longer DIRECT) --; it never picks
  * SEPARABLE, because the choice depends on the PSF values, which a plan does not know: the caller asks
  * jd_psf_separable_rank() and requests JD_CONV_MODE_SEPARABLE (jolideco_amd.NPredModel does). */
 enum {
@@ -97,7 +98,10 @@ int jd_conv_plan_shape(const jd_conv_plan* plan, int* shape6);
 /* 0 = FFT, 1 = DIRECT, 2 = SEPARABLE */
 int jd_conv_plan_method(const jd_conv_plan* plan);
 /* 1 when a plan of this geometry with the FFT method runs the hand-written transforms of csrc/fftnative.hip (and with them
- * the batched joint steps), 0 when it runs rocFFT (a size the native kernels do not cover, or option JD_FFT_NATIVE=0).
+ * the batched joint steps), 0 when it runs rocFFT (a size the native kernels do not cover -- padded rows beyond 9216 points,
+ * padded image halves beyond 4608 rows, images narrower than 8 pixels or shorter than two PSFs -- or option JD_FFT_NATIVE=0).
+ * A native plan of the largest size holds 0.64 GB of work arrays and 0.34 GB per kernel spectrum; jd_conv_plan_create
+ * answers JD_ERR_ALLOC where the device has no room for them.
  * Host logic only, no device needed: a caller that is about to embed PSFs of different sizes in one array so that their
  * datasets share a plan (jolideco_amd/models/npred.py common_kernel_shape) asks first. */
 int jd_conv_native_fft_supported(int H, int W, int kh, int kw);
@@ -111,7 +115,8 @@ int jd_conv_plan_takes_walk(const jd_conv_plan* plan, int n_datasets);
  * to pin a case to the kernel it means to check.  route8 =
  *   [0], [1]  Nx, Ny: lengths of the native row / column transforms (0: not a native FFT plan)
  *   [2], [3]  row schedule of the forward-row launch and of the pooled middle launch: 0 generic-large, 1 2304, 2 4608,
- *             3 1152, 4 generic-small, 5 one-wave tiny; -1: no such launch
+ *             3 1152, 4 generic-small, 5 one-wave tiny, 6 generic-huge (rows beyond 4608 points or 5120 pixels, up to
+ *             9216: 768 threads per row pair); -1: no such launch
  *   [4]       1 when the fused up-sampled (pooled) launches take this factor and grid
  *   [5]       1 when the column passes exchange pooled row groups with the middle launch
  *   [6]       jd_npred_poisson_calibrated_batch_fwd_bwd: 0 per-dataset calls, 1 every launch over all datasets,

@@ -6,7 +6,7 @@
 //           both independently -- zero padded to Nx, complex FFT of length Nx in LDS, spectrum row to HBM.  No padded
 //           real image, no Hermitian bookkeeping: every transform of the path is a plain complex FFT.  With a
 //           calibration the input is the bilinearly shifted image (the shift kernel's arithmetic inside the load).
-//   columns one wave per column (four columns per block; two waves per column for 4096-row images): the H/2 spectrum rows
+//   columns one wave per column (four columns per block; two waves per column for 4096-row images, four beyond): the H/2 spectrum rows
 //           of the column, zero extended to Ny, in LDS and in place: the forward passes but the last; then the last
 //           forward pass, the product with the kernel spectrum K^ (column-major) and the first inverse pass in one
 //           register block (the inverse transform's radices run in reverse order: its first butterfly reads what the
@@ -21,8 +21,8 @@
 //   epilogue; for the datasets of a joint step every launch covers all of them (FftBatch).
 //
 // Row and column lengths of 1024- / 2048- / 4096-pixel images run kernels whose radix schedule, length and loop bounds are
-// template parameters; the generic runtime-radix kernels serve every other length 2^a * {1, 3, 9} (jd_fftcore.h), rocFFT
-// everything else.
+// template parameters; the generic runtime-radix kernels serve every other length 2^a * {1, 3, 9} (jd_fftcore.h) up to 9216
+// points of a row and 4608 of a column (images up to 9216 columns x 2 * 4608 rows less the PSF's halo), rocFFT everything else.
 //
 // HBM traffic of one forward convolution at 2048^2 with a 33 x 33 PSF (Nx = 2304, Ny = 1152): 33.6 MB in, 18.9 MB
 // spectrum out, 18.9 + 21.2 (K^) in, 21.2 out, 21.2 in, 16.8 out = 152 MB against rocFFT's ~6 passes over a 2100 x 2100
@@ -123,13 +123,21 @@ __device__ __forceinline__ float2* fft_lds(float2* a, float2* b, int N, const Ff
 // and <0, 0, 0, 0> for everything else.
 // <0, 0, 0, 2>: rows of at most GENERIC_TINY points on ONE wave (round 5: a 768-point row is 48 radix-16 butterflies per pass --
 // a 256-thread block idles through them and pays block barriers between the passes; one wave per row pair fences instead).
-constexpr int GENERIC_TINY = 1024, GENERIC_SMALL = 1536, GENERIC_LARGE = 5120;
+// <0, 0, 0, 3>: rows beyond GENERIC_LARGE pixels or 4608 points, up to GENERIC_HUGE of either (8192-column images: 9216 =
+// 16 * 8 * 8 * 9) on 768 threads -- twelve waves, three per SIMD and so up to 168 registers; the two padded sequences are
+// 157 KB of the CU's 160 KB of LDS: one block per CU.  A pass is 576 radix-16, 1152 radix-8 or 1024 radix-9 butterflies.
+constexpr int GENERIC_TINY = 1024, GENERIC_SMALL = 1536, GENERIC_LARGE = 5120, GENERIC_HUGE = 9216;
+constexpr int ROW_MAX_POINTS_LARGE = 4608;  // longest transform of the <0, 0, 0, 0> kernels (256 threads, five pieces each)
 template <int R0, int R1, int R2, int R3>
 struct RowSched {
   static constexpr bool STATIC = R0 > 0;
   static constexpr int N = STATIC ? R0 * R1 * R2 * (R3 ? R3 : 1) : 0;
-  static constexpr int LIMIT = STATIC ? N : R3 == 2 ? GENERIC_TINY : R3 == 1 ? GENERIC_SMALL : GENERIC_LARGE;  // longest row (pixels or points) the kernel takes
-  static constexpr int T = (R0 == 8 && R1 == 8 && R2 == 8 && R3 == 9) ? 576 : (!STATIC && R3 == 2) ? 64 : ROW_THREADS;
+  static constexpr int LIMIT = STATIC ? N : R3 == 3 ? GENERIC_HUGE : R3 == 2 ? GENERIC_TINY : R3 == 1 ? GENERIC_SMALL : GENERIC_LARGE;  // longest row (pixels or points) the kernel takes
+  static constexpr int T = (R0 == 8 && R1 == 8 && R2 == 8 && R3 == 9) ? 576 : (!STATIC && R3 == 2) ? 64 : (!STATIC && R3 == 3) ? 768 : ROW_THREADS;
+  // the batched adjoint launch holds the next dataset's spectrum row and the gradient rows it sums in registers while it
+  // transforms the current row; the 9216-point rows have no registers for either (six 16-byte pieces of the one and of the
+  // other per thread: scratch at 768 and at 1024 threads) -- they load each row when its turn comes and sum in `out`
+  static constexpr bool BATCH_IN_REGS = !(!STATIC && R3 == 3);
   static constexpr int WAVES_PER_SIMD = T == 576 ? 5 : 1;  // (two blocks of nine waves: five on one SIMD -> at most 96 registers)
   static constexpr int MAXQ = (LIMIT + 4 * T - 1) / (4 * T);  // 16-byte pieces of an image row per thread
   static constexpr int PRE = (LIMIT + 2 * T - 1) / (2 * T);   // 16-byte pieces of a spectrum row per thread
@@ -323,14 +331,19 @@ __device__ __forceinline__ void column_mid_inplace(float2* x_, int N, const floa
 
 // butterflies per thread (N / R / LANES rounded up) the instantiations hold: 2 / 3 / 2 / 2 at radix 16 / 8 / 9 / 4 --
 // one wave per column up to N = 1152 (16: 72 butterflies, 8: 144, 9: 128) and N = 1024, two waves up to 2304 (144 / 256 /
-// 256) and 2048; 0: the length is not a column length (radix 2 or 3 passes, a single pass, or too long)
+// 256) and 2048, four waves beyond (4608 = 8 * 8 * 8 * 9: 576 / 512 butterflies, 3 / 2 per thread; 4096 = 16 * 16 * 16: ONE
+// radix-16 butterfly per thread -- the two of the two-wave form cost 168 registers and scratch, and a block of two such
+// columns, all LDS lets a CU hold of them twice, would be four waves); 0: the length is not a column length (radix 2 or 3
+// passes, a single pass, or too long)
+constexpr int COLUMN_TWO_WAVE_MAX = 2304, COLUMN_MAX = 4608;
 __host__ __device__ inline int column_lanes(int N, const FftPasses& f) {
-  if (f.n < 2) return 0;
-  for (int lanes = 64; lanes <= 128; lanes *= 2) {
+  if (f.n < 2 || N > COLUMN_MAX) return 0;
+  const int first = N > COLUMN_TWO_WAVE_MAX ? 256 : 64, last = N > COLUMN_TWO_WAVE_MAX ? 256 : 128;
+  for (int lanes = first; lanes <= last; lanes *= 2) {
     bool ok = true;
     for (int s = 0; s < f.n; ++s) {
       const int R = f.r[s], per = (N / R + lanes - 1) / lanes;
-      ok = ok && ((R == 16 && per <= 2) || (R == 8 && per <= 3) || (R == 9 && per <= 2) || (R == 4 && per <= 2));
+      ok = ok && ((R == 16 && per <= (lanes == 256 ? 1 : 2)) || (R == 8 && per <= 3) || (R == 9 && per <= 2) || (R == 4 && per <= 2));
     }
     if (ok) return lanes;
   }
@@ -340,7 +353,7 @@ __host__ __device__ inline int column_lanes(int N, const FftPasses& f) {
 template <int DIR, int LANES, bool POW2>
 __device__ __forceinline__ void column_pass_any(int R, float2* x, int N, int p, const float2* tw, int lane) {
   switch (R) {
-    case 16: column_pass_inplace<16, DIR, 2, LANES, POW2>(x, N, p, tw, lane); break;
+    case 16: column_pass_inplace<16, DIR, (LANES == 256 ? 1 : 2), LANES, POW2>(x, N, p, tw, lane); break;
     case 8: column_pass_inplace<8, DIR, 3, LANES, POW2>(x, N, p, tw, lane); break;
     case 9: column_pass_inplace<9, DIR, 2, LANES, POW2>(x, N, p, tw, lane); break;
     default: column_pass_inplace<4, DIR, 2, LANES, POW2>(x, N, p, tw, lane); break;
@@ -360,7 +373,7 @@ __device__ __forceinline__ void column_conv_inplace(float2* x, int N, const FftP
   }
   const int Rm = f.r[f.n - 1];
   switch (Rm) {
-    case 16: column_mid_inplace<16, 2, LANES>(x, N, tw, kcol, conj, lane); break;
+    case 16: column_mid_inplace<16, (LANES == 256 ? 1 : 2), LANES>(x, N, tw, kcol, conj, lane); break;
     case 8: column_mid_inplace<8, 3, LANES>(x, N, tw, kcol, conj, lane); break;
     case 9: column_mid_inplace<9, 2, LANES>(x, N, tw, kcol, conj, lane); break;
     default: column_mid_inplace<4, 2, LANES>(x, N, tw, kcol, conj, lane); break;
@@ -551,6 +564,12 @@ struct ColsArgs {
 // time constants -- index arithmetic folds, and the kernel holds the five passes it runs instead of every radix in both
 // directions (the generic form is 13 000 instructions, more than the instruction cache); R0 = 0: the generic form.
 constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
+#ifndef JD_COLS256_WAVES
+// waves per SIMD the four-wave column kernel is compiled for.  4: 128 registers + 52 B of scratch, two blocks of 512 threads
+// per CU (78 KB of LDS each); 3: 142 registers, no scratch, one block.  Measured, 4 against 3 (profiles/fft_wide): forward
+// convolution 8192 x 512 94 against 105 us, 8192^2 1078 against 1205, 6000^2 617 against 640.
+#define JD_COLS256_WAVES 4
+#endif
 
 template <int LANES, int R0, int R1, int R2>
 __device__ __forceinline__ void column_conv_static(float2* x, const float2* tw, const float2* kcol, int conj, int lane) {
@@ -564,7 +583,7 @@ __device__ __forceinline__ void column_conv_static(float2* x, const float2* tw, 
 }
 
 template <int LANES, int CBS, int R0, int R1, int R2>
-__global__ __launch_bounds__((LANES * CBS > 512 ? 1024 : 512), (LANES * CBS > 512 ? 4 : 3)) void fftn_cols_kernel(ColsArgs a) {
+__global__ __launch_bounds__((LANES * CBS > 512 ? 1024 : 512), (LANES * CBS > 512 ? 4 : LANES == 256 ? JD_COLS256_WAVES : 3)) void fftn_cols_kernel(ColsArgs a) {
   extern __shared__ float2 lds[];
   constexpr bool STATIC = R0 > 0;
   const int tid = threadIdx.x, lane = tid % LANES, wc = tid / LANES, CB = STATIC ? CBS : (int)blockDim.x / LANES;
@@ -864,15 +883,20 @@ __global__ __launch_bounds__((RowSched<R0, R1, R2, R3>::T), (RowSched<R0, R1, R2
   constexpr int MAXQ = S::MAXQ;
   const size_t o1 = (size_t)y * a.W, o2 = (size_t)(y + a.Hh) * a.W;
   const bool ragged = (a.W & 3) != 0, lower = y + a.Hh < a.H;
-  float4 au[MAXQ], ad[MAXQ];
+  constexpr bool IN_REGS = S::BATCH_IN_REGS;
+  float4 au[IN_REGS ? MAXQ : 1], ad[IN_REGS ? MAXQ : 1];
 #pragma unroll
-  for (int q = 0; q < MAXQ; ++q) au[q] = ad[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 pre[S::PRE];
-  load_spectrum_row_regs<S::T, S::PRE>(pre, a.batch->work[0], Nx, y, a.Hh, a.Ny, a.ra, a.rb, tid);
+  for (int q = 0; q < (IN_REGS ? MAXQ : 1); ++q) au[q] = ad[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 pre[IN_REGS ? S::PRE : 1];
+  if constexpr (IN_REGS) load_spectrum_row_regs<S::T, S::PRE>(pre, a.batch->work[0], Nx, y, a.Hh, a.Ny, a.ra, a.rb, tid);
 #pragma unroll 1
   for (int d = 0; d < a.n_batch; ++d) {
-    store_spectrum_row_regs<S::T, S::PRE>(bufa, pre, Nx, tid);
-    if (d + 1 < a.n_batch) load_spectrum_row_regs<S::T, S::PRE>(pre, a.batch->work[d + 1], Nx, y, a.Hh, a.Ny, a.ra, a.rb, tid);
+    if constexpr (IN_REGS) {
+      store_spectrum_row_regs<S::T, S::PRE>(bufa, pre, Nx, tid);
+      if (d + 1 < a.n_batch) load_spectrum_row_regs<S::T, S::PRE>(pre, a.batch->work[d + 1], Nx, y, a.Hh, a.Ny, a.ra, a.rb, tid);
+    } else {  // (the per-dataset kernel's load: the same sums, no row held across the transform)
+      load_spectrum_row<S::T>(bufa, a.batch->work[d], Nx, y, a.Hh, a.Ny, a.ra, a.rb, tid);
+    }
     const float2* r = row_fft<1, S, R0, R1, R2, R3>(bufa, bufb, Nx, a.f, a.tw, tid);
     const float* scale = a.batch->exposure[d];
     const bool add = d > 0 || a.accumulate;
@@ -889,21 +913,29 @@ __global__ __launch_bounds__((RowSched<R0, R1, R2, R3>::T), (RowSched<R0, R1, R2
       up.x *= s1.x, up.y *= s1.y, up.z *= s1.z, up.w *= s1.w;
       dn.x *= s2.x, dn.y *= s2.y, dn.z *= s2.z, dn.w *= s2.w;
       if (add) {
-        float4 g1 = au[q], g2 = ad[q];
-        if (d == 0) g1 = row_ld4(a.out + o1, x, a.W, ragged), g2 = row_ld4(a.out + o2, x, a.W, ragged, lower);
+        float4 g1 = au[IN_REGS ? q : 0], g2 = ad[IN_REGS ? q : 0];
+        // (!IN_REGS: the sums so far are in `out` -- the same thread wrote these elements for the dataset before)
+        if (d == 0 || !IN_REGS) g1 = row_ld4(a.out + o1, x, a.W, ragged), g2 = row_ld4(a.out + o2, x, a.W, ragged, lower);
         up.x += g1.x, up.y += g1.y, up.z += g1.z, up.w += g1.w;
         dn.x += g2.x, dn.y += g2.y, dn.z += g2.z, dn.w += g2.w;
       }
-      au[q] = up, ad[q] = dn;
+      if constexpr (IN_REGS) {
+        au[q] = up, ad[q] = dn;
+      } else {
+        row_st4(a.out + o1, x, a.W, ragged, up);
+        row_st4(a.out + o2, x, a.W, ragged, dn, lower);
+      }
     }
     __syncthreads();  // the result buffer is the next dataset's work space
   }
+  if constexpr (IN_REGS) {
 #pragma unroll
-  for (int q = 0; q < MAXQ; ++q) {
-    const int x = 4 * (tid + q * S::T);
-    if (x >= a.W) continue;
-    row_st4(a.out + o1, x, a.W, ragged, au[q]);
-    row_st4(a.out + o2, x, a.W, ragged, ad[q], lower);
+    for (int q = 0; q < MAXQ; ++q) {
+      const int x = 4 * (tid + q * S::T);
+      if (x >= a.W) continue;
+      row_st4(a.out + o1, x, a.W, ragged, au[q]);
+      row_st4(a.out + o2, x, a.W, ragged, ad[q], lower);
+    }
   }
   if (a.fin_partials) {
     __shared__ double red[S::T / 64];
@@ -988,7 +1020,7 @@ __global__ __launch_bounds__((RowSched<R0, R1, R2, R3>::T), (RowSched<R0, R1, R2
   __syncthreads();  // every thread has read its part of the convolution row: the buffers are free
   // ---- z = g[y] + i g[y + Hh], zero padded: the adjoint's row transform ---------------------------------------------
 #pragma unroll
-  for (int q = 0; q < MAXQ; ++q) {  // (Nx <= 4608 < 4 * 256 * MAXQ)
+  for (int q = 0; q < MAXQ; ++q) {  // (Nx <= LIMIT <= 4 * T * MAXQ)
     const int x = 4 * (tid + q * S::T), e = lp(x);
     if (x >= Nx) continue;
     float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = u;
@@ -1200,11 +1232,11 @@ bool fftn_supported(int H, int W, int kh, int kw) {
   const int Hh = (H + 1) / 2;
   if (H < 2 || Hh < kh || kh < 1 || kw < 1) return false;
   if (W < 8) return false;  // (the five-pixel windows of a calibrated row load, issue_row5, need W >= 5; narrower images: rocFFT)
-  if (W > 4 * ROW_THREADS * 5) return false;
+  if (W > GENERIC_HUGE) return false;
   const int ox = (kw - 1) / 2;
   const int nx = next_length(W + std::max(ox, kw - 1 - ox)), ny = next_length(Hh + kh - 1, false);
   // LDS: two padded sequences per row block, one per wave of a column block
-  if (!(nx > 0 && ny > 0 && nx <= 4608 && ny <= 2304 && ny >= 2 * kh)) return false;
+  if (!(nx > 0 && ny > 0 && nx <= GENERIC_HUGE && ny <= COLUMN_MAX && ny >= 2 * kh)) return false;
   return factorize(nx).n > 0 && column_lanes(ny, passes_of(ny)) != 0;
 }
 
@@ -1214,8 +1246,12 @@ int fftn_create(FftNative* n, int H, int W, int kh, int kw) {
   n->Hh = (H + 1) / 2;  // (odd H: the lower half is one row short)
   n->Nx = next_length(W + std::max(n->ox, kw - 1 - n->ox));
   n->Ny = next_length(n->Hh + kh - 1, false);
-  JD_HIP(hipMalloc(&n->spec, (size_t)n->Hh * n->Nx * sizeof(float2)));
-  JD_HIP(hipMalloc(&n->work, (size_t)n->Ny * n->Nx * sizeof(float2)));
+  // (9216 x 4608: `work` alone is 340 MB -- a device without room for it answers with an error, not with a crash)
+  if (hipMalloc(&n->spec, (size_t)n->Hh * n->Nx * sizeof(float2)) != hipSuccess ||
+      hipMalloc(&n->work, (size_t)n->Ny * n->Nx * sizeof(float2)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(JD_ERR_ALLOC, "native FFT: hipMalloc of the %d x %d spectrum arrays failed", n->Ny, n->Nx);
+  }
   std::vector<float2> tw;
   for (int pass = 0; pass < 2; ++pass) {
     const int N = pass ? n->Ny : n->Nx;
@@ -1293,7 +1329,7 @@ int launch_cols(const FftNative& n, const float2* khat, int adjoint, hipStream_t
   int cb = static_1152 ? 8 : lanes == 64 || static_two_wave ? 4 : 2;
   while (cb > 2 && n.Nx % cb != 0) cb /= 2;
   const int ocb = opt_value(OPT_FFT_NATIVE, 1);  // (tuning: JD_FFT_NATIVE = 2 / 4 / 8 forces the columns per block)
-  if ((ocb == 2 || ocb == 4 || ocb == 8) && (size_t)ocb * per_col <= 160 * 1024 && n.Nx % ocb == 0 && ocb * lanes <= 1024) cb = ocb;
+  if ((ocb == 2 || ocb == 4 || ocb == 8) && (size_t)ocb * per_col <= 160 * 1024 && n.Nx % ocb == 0 && ocb * lanes <= 1024 && (lanes < 256 || ocb == 2)) cb = ocb;
   a.groups = n.Nx / cb;
   // the kernel of the schedule: compile-time forms for the lengths of the usual image sizes (default columns per block),
   // the generic form for everything else
@@ -1315,6 +1351,7 @@ int launch_cols(const FftNative& n, const float2* khat, int adjoint, hipStream_t
       {64, 4, 8, 8, 8, fftn_cols_kernel<64, 4, 8, 8, 8>},      // 512
       {64, 0, 0, 0, 0, fftn_cols_kernel<64, 0, 0, 0, 0>},      // generic
       {128, 0, 0, 0, 0, fftn_cols_kernel<128, 0, 0, 0, 0>},
+      {256, 0, 0, 0, 0, fftn_cols_kernel<256, 0, 0, 0, 0>},    // 4096 and 4608: images beyond 4600 rows, two columns per block
   };
   Entry* e = nullptr;
   for (Entry& t : table) {
@@ -1331,7 +1368,7 @@ int launch_cols(const FftNative& n, const float2* khat, int adjoint, hipStream_t
 
 // The row kernels by schedule: compile-time forms for the row lengths of the usual image sizes, the generic form
 // otherwise.  Index into every table: row_schedule(f).
-constexpr int N_ROW_SCHED = 6;
+constexpr int N_ROW_SCHED = 7;
 int fftn_cus() {  // compute units of the current device
   static int n_cu = 0;
   if (!n_cu) {
@@ -1348,6 +1385,7 @@ int row_schedule(const FftPasses& f, int Nx, int W, int blocks) {
   if (is(16, 16, 9, 0)) return 1;  // 2304: 2048-column images
   if (is(8, 8, 8, 9)) return 2;    // 4608: 4096-column images
   if (is(16, 8, 9, 0)) return 3;   // 1152: 1024-column images
+  if (Nx > ROW_MAX_POINTS_LARGE || W > GENERIC_LARGE) return 6;  // up to 9216 points or pixels: 768 threads
   // one wave per row where the launch has rows enough to fill the chip with waves (8 batched datasets at 512^2: 2592 row
   // pairs, 150 -> 126 us per step); a launch of few rows (one dataset: 384) is done sooner with four waves on each
   // (e0102, sequential: 0.240 against 0.263 ms per step)
@@ -1357,7 +1395,7 @@ int row_schedule(const FftPasses& f, int Nx, int W, int blocks) {
 }
 #define JD_ROW_KERNELS(NAME, ...)                                                                          \
   {NAME<__VA_ARGS__ 0, 0, 0, 0>, NAME<__VA_ARGS__ 16, 16, 9, 0>, NAME<__VA_ARGS__ 8, 8, 8, 9>, NAME<__VA_ARGS__ 16, 8, 9, 0>, \
-   NAME<__VA_ARGS__ 0, 0, 0, 1>, NAME<__VA_ARGS__ 0, 0, 0, 2>}
+   NAME<__VA_ARGS__ 0, 0, 0, 1>, NAME<__VA_ARGS__ 0, 0, 0, 2>, NAME<__VA_ARGS__ 0, 0, 0, 3>}
 
 template <class Args>
 int launch_row_kernel(void (*const (&kernels)[N_ROW_SCHED])(Args), const FftNative& n, const Args& a,
@@ -1368,7 +1406,7 @@ int launch_row_kernel(void (*const (&kernels)[N_ROW_SCHED])(Args), const FftNati
   if (rc) return rc;
   ProfScope prof(kernel_id, stream);
   static constexpr int threads[N_ROW_SCHED] = {RowSched<0, 0, 0, 0>::T, RowSched<16, 16, 9, 0>::T, RowSched<8, 8, 8, 9>::T, RowSched<16, 8, 9, 0>::T,
-                                               RowSched<0, 0, 0, 1>::T, RowSched<0, 0, 0, 2>::T};
+                                               RowSched<0, 0, 0, 1>::T, RowSched<0, 0, 0, 2>::T, RowSched<0, 0, 0, 3>::T};
   hipLaunchKernelGGL(kernels[sched], dim3(blocks ? blocks : n.Hh), dim3(threads[sched]), lds_rows, stream, a);
   JD_LAUNCH_CHECK();
   return JD_OK;
@@ -1441,7 +1479,7 @@ int fftn_poisson_step(const FftNative& n, const float* flux, const float* exposu
 // norm_grad_scale * sum(g * background) are finalised by blocks 0 and 1 of the last launch.
 bool fftn_pooled_supported(const FftNative& n, int upsampling) {
   return upsampling >= 2 && upsampling <= 4 && n.W % upsampling == 0 && n.H % (2 * upsampling) == 0 && n.Hh / upsampling >= 2 &&
-         n.W <= 4 * ROW_THREADS * 5;
+         n.W <= GENERIC_HUGE;
 }
 
 namespace {

@@ -145,14 +145,14 @@ class ConvPlan:
     @property
     def native_fft(self):
         """True when an "fft" plan runs on the hand-written transforms of csrc/fftnative.hip (no padded grid) instead of
-        rocFFT (padded sizes 2^a * {1, 3, 9} up to 4608 columns x 2304 row pairs; any H, W since round 5; option JD_FFT_NATIVE=0 switches it off)."""
+        rocFFT (padded sizes 2^a * {1, 3, 9} up to 9216 columns x 4608 row pairs; any H, W since round 5; option JD_FFT_NATIVE=0 switches it off)."""
         return self.method == "fft" and (self.Hp, self.Wp) == (self.H, self.W)
 
     def takes_walk(self, n_datasets=1):
         """True when a launch over ``n_datasets`` datasets runs on the strip-walk kernels (jd_conv_plan_takes_walk)."""
         return bool(_hip.lib().jd_conv_plan_takes_walk(self._handle, int(n_datasets)))
 
-    ROW_SCHEDULES = ("generic-large", "2304", "4608", "1152", "generic-small", "tiny")  # row_schedule of csrc/fftnative.hip
+    ROW_SCHEDULES = ("generic-large", "2304", "4608", "1152", "generic-small", "tiny", "generic-huge")  # row_schedule of csrc/fftnative.hip
 
     def step_route(self, upsampling=1, n_datasets=1):
         """The kernels a likelihood step of ``n_datasets`` datasets with this up-sampling factor launches
