@@ -491,6 +491,29 @@ int jd_add_rolled_bands_step(int H, int W, int shift_y, int shift_x, const float
  * (patches/gmm.py:262-281).  x: (n, D) device (D of the handle: 64 or 256), out: (n, K) device. */
 int jd_gmm_estimate_log_prob(jd_gmm* gmm, const float* x, int n, float* out, void* stream);
 
+/* FITTING A MIXTURE (csrc/gmm_fit.hip): the device half of one EM step of a full-covariance Gaussian mixture, as in
+ * sklearn.mixture.GaussianMixture(covariance_type="full").  With d_nk = x_n - means[k], l_nk = const_k[k] -
+ * |prec_chol[k]^T d_nk|^2 / 2, lse_n = logsumexp_k l_nk (max-shifted) and r_nk = exp(l_nk - lse_n), jd_gmm_fit_step
+ * writes K + K D + K D D + 1 doubles to sums_out:
+ *   [sum_n r_nk (K) | sum_n r_nk d_nk (K, D) | sum_n r_nk d_nk d_nk^T (K, D, D) | sum_n lse_n] .
+ * The moments are about the means the call was given; the caller finishes the M-step on the host in float64.
+ * x (n, D), means (K, D), prec_chol (K, D, D: UPPER TRIANGULAR factors P_k, row major; entries below the diagonal are
+ * never read), const_k (K) = log w_k + log det P_k - D/2 log 2 pi and sums_out are DEVICE pointers, borrowed for the
+ * call; x needs float alignment only, and its alignment changes no bit of the result.  The whitening runs on
+ * v_mfma_f32_16x16x4_f32; the moments are accumulated in float64 (the second ones on v_mfma_f64_16x16x4_f64, from exact
+ * products).  No atomics: blocks add into float64 partial sums of their own
+ * and a second launch adds those in a fixed order, so two calls on the same input give the same bits.
+ * The handle owns the partial sums: at most max_blocks sets of K (D D + D + 1) doubles, max_blocks = 0 selecting the
+ * default, the number of compute units, lowered where the sets would exceed 8 GiB.  They are allocated by the first step
+ * and whenever a step needs more sets than any before it; apart from that a step allocates nothing and never
+ * synchronises.  Supported: D = 64 or 256, 1 <= K <= 1024, 1 <= n <= (2^31 - 1) / D.  Anything else, a null handle and
+ * null pointers return JD_ERR_INVALID with a message and launch nothing.  jd_gmm_fit_destroy(NULL) is a no-op. */
+typedef struct jd_gmm_fit jd_gmm_fit;
+int jd_gmm_fit_create(int D, int K, int max_blocks, jd_gmm_fit** fit_out);
+int jd_gmm_fit_destroy(jd_gmm_fit* fit);
+int jd_gmm_fit_step(jd_gmm_fit* fit, const float* x, long long n, const float* means, const float* prec_chol,
+                    const float* const_k, double* sums_out, void* stream);
+
 /* Element-wise priors: InverseGammaPrior (priors/core.py:207-226; kind 1: alpha, beta) and
  * ExponentialPrior (priors/core.py:308-326; kind 2: alpha).  value_out <- sum(v)/n + log_const;
  * grad_flux_accum += grad_coef * d value / d flux. */

@@ -19,6 +19,7 @@ from ._hip import check, ptr, ptr_array, stream_ptr
 __all__ = [
     "ConvPlan",
     "GmmHandle",
+    "GmmFitHandle",
     "ConvSameFunction",
     "PoissonNLLFunction",
     "GMMPatchPriorFunction",
@@ -884,3 +885,54 @@ def adam_bias_terms(step, lr, beta1, beta2):
     bias1 = 1 - beta1**step
     bias2 = 1 - beta2**step
     return lr / bias1, math.sqrt(bias2)
+
+
+class GmmFitHandle:
+    """Work space of the EM step kernel (jd_gmm_fit, csrc/gmm_fit.hip) for mixtures of ``n_components`` components over
+    ``n_features`` = 64 or 256 features on one device.  ``max_blocks`` bounds the sets of partial sums (0: the default)."""
+
+    def __init__(self, n_features, n_components, device, max_blocks=0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("GmmFitHandle needs a HIP device (no CPU fallback)")
+        self.D, self.K = int(n_features), int(n_components)
+        handle = c_void_p()
+        with torch.cuda.device(self.device):
+            check(_hip.lib().jd_gmm_fit_create(self.D, self.K, int(max_blocks), ctypes.byref(handle)))
+        self._handle = handle
+        size = self.K * (1 + self.D + self.D * self.D) + 1
+        self.sums = torch.empty(size, dtype=torch.float64, device=self.device)
+        self._host = torch.empty(size, dtype=torch.float64).pin_memory()
+
+    def close(self):
+        if self._handle is not None:
+            _hip.lib().jd_gmm_fit_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, x, means, precisions_cholesky, const_k):
+        """The sums of one E-step over the patches ``x`` (n, D) for float32 device parameters: float64 numpy arrays
+        ``(sum r (K,), sum r d (K, D), sum r d d^T (K, D, D), sum lse)`` with d = x - means[k]; synchronises on the copy."""
+        K, D = self.K, self.D
+        x = require_hip_tensor(x, "patches")
+        if x.ndim != 2 or x.shape[1] != D or not x.is_contiguous():
+            raise ValueError(f"patches must be a contiguous (n, {D}) tensor, got {tuple(x.shape)}")
+        for t, shape, name in ((means, (K, D), "means"), (precisions_cholesky, (K, D, D), "precisions_cholesky"), (const_k, (K,), "const_k")):
+            require_hip_tensor(t, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+        with torch.cuda.device(self.device):
+            check(_hip.lib().jd_gmm_fit_step(self._handle, ptr(x), x.shape[0], ptr(means), ptr(precisions_cholesky), ptr(const_k),
+                                             c_void_p(self.sums.data_ptr()), stream_ptr(self.device)))
+            self._host.copy_(self.sums, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        flat = self._host.numpy()
+        s0 = flat[:K].copy()
+        s1 = flat[K:K + K * D].reshape(K, D).copy()
+        s2 = flat[K + K * D:K + K * D + K * D * D].reshape(K, D, D).copy()
+        return s0, s1, s2, float(flat[-1])

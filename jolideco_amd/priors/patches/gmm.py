@@ -5,7 +5,7 @@ Cholesky -> precision Cholesky -> fp32), then handed to the HIP library which la
 MFMA fragment order.  The trained GMM libraries of the reference ("zoran-weiss", ...) are external
 data files that are not part of this repository: `from_registry` / `read` load them from
 ``$JOLIDECO_GMM_LIBRARY`` exactly as the reference does (gmm.py:301-391,493-508) when the user has them;
-`from_numpy` takes explicit arrays.
+`from_numpy` takes explicit arrays; `fit` / `fit_images` train a mixture on the user's own patches (EM, csrc/gmm_fit.hip).
 """
 import json
 import os
@@ -53,6 +53,89 @@ def get_gmm_registry():
         return json.load(f)
 
 
+def em_m_step(means, sum_r, sum_rd, sum_rdd, n, reg_covar):
+    """Finish the M-step of EM in float64 from the weighted moments about the current ``means`` (K, D):
+    ``sum_r`` (K,) = sum_n r_nk, ``sum_rd`` (K, D) = sum_n r_nk d, ``sum_rdd`` (K, D, D) = sum_n r_nk d d^T, d = x_n - means[k].
+    With N_k = sum_r + 10 eps (scikit-learn's guard) and delta = sum_rd / N_k the new mean is means + delta, and the
+    moments about it are sum_rdd - delta sum_rd^T - sum_rd delta^T + sum_r delta delta^T.  Returns (means, covariances,
+    weights); the covariances are symmetrised and carry the ridge ``reg_covar``."""
+    N = sum_r + 10 * np.finfo(np.float64).eps
+    delta = sum_rd / N[:, None]
+    new_means = means + delta
+    outer = delta[:, :, None] * delta[:, None, :]
+    cov = sum_rdd / N[:, None, None] - (2.0 - sum_r / N)[:, None, None] * outer
+    cov = 0.5 * (cov + cov.transpose(0, 2, 1))
+    D = means.shape[1]
+    cov[:, np.arange(D), np.arange(D)] += reg_covar
+    weights = N / n
+    return new_means, cov, weights / weights.sum()
+
+
+def _upload(array, device):
+    return torch.from_numpy(np.ascontiguousarray(array, dtype=np.float32)).to(device)
+
+
+def em_step(handle, patches, means, covariances, weights, reg_covar):
+    """One EM step of `GaussianMixtureModel.fit`: the float64 parameters go to the device as float32 means, precision
+    factors (`compute_precision_cholesky`) and constants log w_k + log det P_k - D/2 log 2 pi (of the ROUNDED factors, so
+    that the densities the device evaluates are normalised), ``handle`` (`ops.GmmFitHandle`) sums the responsibilities
+    and the moments about those float32 means over ``patches``, and `em_m_step` finishes in float64.
+    Returns (means, covariances, weights, lower bound, sum of the responsibilities per component)."""
+    K, D = means.shape
+    n = patches.shape[0]
+    device = patches.device
+    means32 = means.astype(np.float32)
+    prec32 = np.empty((K, D, D), dtype=np.float32)
+    for k in range(K):
+        try:
+            prec32[k] = compute_precision_cholesky(covariances[k : k + 1])[0]
+        except ValueError as exc:
+            raise ValueError(
+                f"the covariance of component {k} is not positive definite (largest entry {np.abs(covariances[k]).max():.3g}, "
+                f"reg_covar = {reg_covar:g}); raise reg_covar or rescale the patches"
+            ) from exc
+    diag = prec32.reshape(K, -1)[:, :: D + 1].astype(np.float64)
+    const = np.log(weights) + np.log(diag).sum(axis=1) - 0.5 * D * np.log(2 * np.pi)
+    s0, s1, s2, lse_sum = handle.step(patches, _upload(means32, device), _upload(prec32, device), _upload(const, device))
+    new_means, new_cov, new_weights = em_m_step(means32.astype(np.float64), s0, s1, s2, n, reg_covar)
+    return new_means, new_cov, new_weights, lse_sum / n, s0
+
+
+def random_start(patches, n_components, reg_covar=1e-6, random_state=0):
+    """The start `GaussianMixtureModel.fit` takes when it is given none: ``n_components`` distinct patches drawn by
+    ``numpy.random.RandomState(random_state)`` as means, the covariance of all patches + ``reg_covar`` I for every
+    component, uniform weights -- float64 (means, covariances, weights).  Mean and covariance of the patches come from the
+    step kernel itself: one component with P = I and c = 0 has r = 1; a pass about zero gives the mean, a second one about
+    that mean the moments."""
+    from ...ops import GmmFitHandle
+
+    n, D = patches.shape
+    device = patches.device
+    one = _fit_handle(GmmFitHandle, device, D, 1)
+    eye, zero = _upload(np.eye(D)[None], device), _upload(np.zeros(1), device)
+    _, s1, _, _ = one.step(patches, _upload(np.zeros((1, D)), device), eye, zero)
+    centre = (s1 / n).astype(np.float32)
+    s0, s1, s2 = one.step(patches, _upload(centre, device), eye, zero)[:3]
+    _, cov_all, _ = em_m_step(centre.astype(np.float64), s0, s1, s2, n, reg_covar)
+    index = np.sort(np.random.RandomState(random_state).choice(n, n_components, replace=False))
+    means = patches[torch.from_numpy(index).to(device)].cpu().numpy().astype(np.float64)
+    return means, np.repeat(cov_all, n_components, axis=0), np.full(n_components, 1.0 / n_components)
+
+
+_FIT_HANDLES = {}
+
+
+def _fit_handle(handle_cls, device, n_features, n_components):
+    """The fit work space of (device, D, K), created on first use and kept: later fits of the size allocate nothing."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (str(device), int(n_features), int(n_components))
+    if key not in _FIT_HANDLES:
+        _FIT_HANDLES[key] = handle_cls(n_features, n_components, device)
+    return _FIT_HANDLES[key]
+
+
 class GaussianMixtureModel:
     """Gaussian mixture model with full covariances.
 
@@ -67,6 +150,7 @@ class GaussianMixtureModel:
         self.precisions_cholesky_numpy = np.asarray(precisions_cholesky, dtype=np.float32)
         self.meta = meta or GaussianMixtureModelMeta()
         self.registry_name = None
+        self.fit_info = None  # set by `fit`
         self._handles = {}
 
     @classmethod
@@ -147,6 +231,135 @@ class GaussianMixtureModel:
             meta={"PNPTYPE": self.meta.patch_norm.to_dict()["type"]},
         )
         write_fits(filename, [HDU(kind="primary"), HDU(table, name="GMM")], overwrite=overwrite)
+
+    # fitting -------------------------------------------------------------------------------
+    @classmethod
+    def fit(cls, patches, n_components=None, *, init=None, means_init=None, covariances_init=None, weights_init=None,
+            n_iter=100, tol=1e-3, reg_covar=1e-6, random_state=0, meta=None):
+        """Fit a full-covariance mixture to ``patches`` by EM on the GPU, with the steps of
+        ``sklearn.mixture.GaussianMixture(covariance_type="full")``.
+
+        patches : HIP float32 tensor (n, D), D = 64 or 256, already normalised (see `fit_images`).
+        The start is a model ``init``, or the three arrays ``means_init`` (K, D), ``covariances_init`` (K, D, D) and
+        ``weights_init`` (K,), or -- with ``n_components`` alone -- K distinct patches drawn by
+        ``numpy.random.RandomState(random_state)`` as means, the covariance of all patches + ``reg_covar`` I for every
+        component and uniform weights.  That start is deterministic; it is NOT scikit-learn's k-means start, so the
+        two packages agree step by step only from a common explicit start.
+
+        Every step is one pass of the device over the patches (csrc/gmm_fit.hip: responsibilities, and the weighted
+        moments about the current means); the division, the mean correction, the ridge and the Cholesky factors are done
+        on the host in float64 and K D^2 floats are uploaded.  The iteration stops when the mean log-likelihood changes by
+        less than ``tol`` or after ``n_iter`` steps.  A component whose weight sum falls below D cannot carry a
+        covariance: ValueError names it.
+
+        Returns a model built by `from_numpy` from the float64 result, carrying ``meta`` and a ``fit_info`` dict with
+        ``lower_bounds`` (one per step), ``converged``, ``n_iter`` and the float64 ``means``, ``covariances``, ``weights``."""
+        from ...ops import GmmFitHandle
+
+        given = [a is not None for a in (means_init, covariances_init, weights_init)]
+        if init is not None and any(given):
+            raise ValueError("give either `init` or means_init / covariances_init / weights_init, not both")
+        if any(given) and not all(given):
+            raise ValueError("means_init, covariances_init and weights_init are given together or not at all")
+        if not isinstance(patches, torch.Tensor) or patches.ndim != 2 or patches.dtype != torch.float32:
+            raise ValueError("patches must be a float32 torch tensor of shape (n, D)")
+        n, D = int(patches.shape[0]), int(patches.shape[1])
+        if D not in (64, 256):
+            raise ValueError(f"patches of D = 64 or D = 256 features only, got D = {D}")
+        if n < 1 or n > (2**31 - 1) // D:
+            raise ValueError(f"1 <= n <= (2^31 - 1) / D patches, got n = {n}")
+        if init is not None:
+            means = init.means_numpy.astype(np.float64)
+            covariances = init.covariances_numpy.astype(np.float64)
+            weights = init.weights_numpy.astype(np.float64)
+        elif all(given):
+            means = np.array(means_init, dtype=np.float64)
+            covariances = np.array(covariances_init, dtype=np.float64)
+            weights = np.array(weights_init, dtype=np.float64)
+        else:
+            means = covariances = weights = None
+        if means is not None:
+            K = means.shape[0] if means.ndim == 2 else -1
+            if means.shape != (K, D) or covariances.shape != (K, D, D) or weights.shape != (K,):
+                raise ValueError(
+                    f"start of shapes {means.shape}, {covariances.shape}, {weights.shape} does not fit (K, {D}), (K, {D}, {D}), (K,)"
+                )
+            if n_components is not None and int(n_components) != K:
+                raise ValueError(f"n_components = {n_components} but the start has {K} components")
+        else:
+            if n_components is None:
+                raise ValueError("n_components is needed without a start")
+            K = int(n_components)
+            if K > n:
+                raise ValueError(f"{K} distinct patches as means need n >= {K}, got n = {n}")
+        if not 1 <= K <= 1024:
+            raise ValueError(f"1 <= n_components <= 1024, got {K}")
+        if int(n_iter) < 1:
+            raise ValueError("n_iter must be at least 1")
+        if not patches.is_cuda:
+            raise RuntimeError("patches must be a HIP tensor: jolideco_amd has no CPU path")
+        patches = patches.contiguous()
+        device = patches.device
+
+        if means is None:
+            means, covariances, weights = random_start(patches, K, reg_covar, random_state)
+
+        handle = _fit_handle(GmmFitHandle, device, D, K)
+        lower_bounds, converged = [], False
+        previous = -np.inf
+        for _ in range(int(n_iter)):
+            means, covariances, weights, lower_bound, sum_r = em_step(handle, patches, means, covariances, weights, reg_covar)
+            starved = np.flatnonzero(~(sum_r >= D))
+            if starved.size:
+                raise ValueError(
+                    f"component {int(starved[0])} is starved: its responsibilities sum to {sum_r[starved[0]]:.3g}, fewer than "
+                    f"the D = {D} patches a covariance needs (components {starved.tolist()}); choose another start or fewer components"
+                )
+            lower_bounds.append(lower_bound)
+            if abs(lower_bound - previous) < tol:
+                converged = True
+                break
+            previous = lower_bound
+        model = cls.from_numpy(means, covariances, weights, meta=meta)
+        # (the float64 parameters as well: the model's own arrays are their float32 roundings)
+        model.fit_info = {"lower_bounds": lower_bounds, "converged": converged, "n_iter": len(lower_bounds),
+                          "means": means, "covariances": covariances, "weights": weights}
+        return model
+
+    @classmethod
+    def fit_images(cls, images, patch_shape=(8, 8), stride=None, patch_norm=None, **fit_kwargs):
+        """`fit` on the overlapping patches of HIP images: one (H, W) tensor, a (B, H, W) tensor or a list of images.
+
+        The patches are cut with ``unfold`` at ``stride`` (default: half the patch edge); those that fail the prior's own
+        ``> -1e5`` filter or hold non-finite values, before or after the norm, are dropped; ``patch_norm`` (default:
+        subtract-mean) is applied in its host form.  The result's ``meta`` holds the stride and the patch norm, so it goes
+        into ``GMMPatchPrior(gmm=...)`` and `write` as it is."""
+        if "meta" in fit_kwargs:
+            raise ValueError("fit_images sets `meta` itself (stride and patch norm)")
+        ph, pw = (int(v) for v in patch_shape)
+        if ph != pw or ph * pw not in (64, 256):
+            raise ValueError(f"patch_shape (8, 8) or (16, 16) only, got {tuple(patch_shape)}")
+        stride = ph // 2 if stride is None else int(stride)
+        if stride < 1:
+            raise ValueError("stride must be positive")
+        patch_norm = SubtractMeanPatchNorm() if patch_norm is None else patch_norm
+        if isinstance(images, torch.Tensor):
+            images = [images] if images.ndim == 2 else list(images)
+        rows = []
+        for image in images:
+            if not (isinstance(image, torch.Tensor) and image.is_cuda):
+                raise RuntimeError("images must be HIP tensors: jolideco_amd has no CPU path")
+            if image.ndim != 2 or image.shape[0] < ph or image.shape[1] < pw:
+                raise ValueError(f"every image must be 2-d and at least {ph} x {pw}, got {tuple(image.shape)}")
+            cut = image.to(torch.float32).unfold(0, ph, stride).unfold(1, pw, stride).reshape(-1, ph * pw)
+            cut = cut[((cut > -1e5) & torch.isfinite(cut)).all(dim=1)]  # patches/core.py:215
+            normed = patch_norm(cut)
+            rows.append(normed[torch.isfinite(normed).all(dim=1)])
+        if not rows:
+            raise ValueError("no images")
+        patches = torch.cat(rows).contiguous()
+        meta = GaussianMixtureModelMeta(stride=stride, patch_norm=patch_norm)
+        return cls.fit(patches, meta=meta, **fit_kwargs)
 
     @property
     def n_components(self):
