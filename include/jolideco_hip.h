@@ -513,6 +513,31 @@ int jd_gmm_fit_create(int D, int K, int max_blocks, jd_gmm_fit** fit_out);
 int jd_gmm_fit_destroy(jd_gmm_fit* fit);
 int jd_gmm_fit_step(jd_gmm_fit* fit, const float* x, long long n, const float* means, const float* prec_chol,
                     const float* const_k, double* sums_out, void* stream);
+/* The same sums for HARD assignments, r_nk = [labels[n] == k] (the k-means start of the fit): no whitening, the last
+ * slot (sum lse) is 0, the layout, the float64 accumulation, the fixed order and the limits are those of jd_gmm_fit_step.
+ * labels (n, int32, device) is only compared with k: a label outside [0, K) contributes to nothing. */
+int jd_gmm_fit_step_labels(jd_gmm_fit* fit, const float* x, long long n, const float* means, const int* labels,
+                           double* sums_out, void* stream);
+
+/* K-MEANS ON PATCHES (csrc/kmeans.hip): one Lloyd step.  With the scores s_nk = |centres[k]|^2 - 2 x_n . centres[k]
+ * (float32 products on v_mfma_f32_16x16x4_f32; |c|^2 summed in float64 and rounded once) jd_kmeans_step writes
+ *   labels[n] = argmin_k s_nk, the lowest k on a tie, and -1 for a patch one of whose scores is not finite, and
+ *   K + K D + 3 doubles to sums_out: [count_k (K) | sum of the patches of cluster k (K, D) | inertia | changed | unassigned],
+ * inertia = sum_n max(|x_n|^2 + s_n,label, 0) evaluated in float64 for the chosen centre, changed = the number of patches
+ * whose label differs from the value labels[n] held on entry, unassigned = the number of labels -1 (such patches are in no
+ * sum).  x (n, D), centres (K, D), labels (n, read and written) and sums_out are DEVICE pointers, borrowed for the call;
+ * float alignment is enough for x.  The cluster sums are accumulated in float64 (exact products on
+ * v_mfma_f64_16x16x4_f64).  No atomics: blocks write partial sums of their own and a last launch adds them in block
+ * order, so two calls on the same input give the same bits.  The handle owns the partial sums (at most max_blocks sets of
+ * K (D + 1) + 3 doubles; 0 selects the default, twice the number of compute units), allocated by the first step and when a
+ * step needs more sets than any before it; apart from that a step allocates nothing and never synchronises.
+ * Supported: D = 64 or 256, 1 <= K <= 1024, 1 <= n <= (2^31 - 1) / D.  Anything else, a null handle and null pointers
+ * return JD_ERR_INVALID with a message and launch nothing.  jd_kmeans_destroy(NULL) is a no-op. */
+typedef struct jd_kmeans jd_kmeans;
+int jd_kmeans_create(int D, int K, int max_blocks, jd_kmeans** kmeans_out);
+int jd_kmeans_destroy(jd_kmeans* kmeans);
+int jd_kmeans_step(jd_kmeans* kmeans, const float* x, long long n, const float* centres, int* labels, double* sums_out,
+                   void* stream);
 
 /* Element-wise priors: InverseGammaPrior (priors/core.py:207-226; kind 1: alpha, beta) and
  * ExponentialPrior (priors/core.py:308-326; kind 2: alpha).  value_out <- sum(v)/n + log_const;

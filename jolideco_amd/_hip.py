@@ -114,6 +114,10 @@ EXPORTS = {
     "jd_gmm_fit_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "jd_gmm_fit_destroy": (c_int, [c_void_p]),
     "jd_gmm_fit_step": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jd_gmm_fit_step_labels": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "jd_kmeans_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
+    "jd_kmeans_destroy": (c_int, [c_void_p]),
+    "jd_kmeans_step": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
     "jd_elementwise_prior_fwd_bwd": (
         c_int,
         [c_int, c_void_p, c_size_t, c_float, c_float, c_float, c_void_p, c_float, c_void_p, c_void_p],

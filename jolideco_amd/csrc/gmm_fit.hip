@@ -245,6 +245,83 @@ __global__ __launch_bounds__(256) void gmm_fit_kernel(GmmFitArgs a) {
   if (threadIdx.x == 0) a.lse_partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The moments of HARD assignments, r_nk = [labels[n] == k] (the k-means start of the fit): phase 2 of the kernel above with
+// the labels of the chunk in LDS in place of the responsibilities and no whitening.  A tile that holds no patch of the
+// component is skipped (a block-uniform vote), so a component costs its own patches' tiles and not all of them.  A label is
+// only ever COMPARED with k: one outside [0, K) matches no component and contributes nothing.  The lse slot is 0.
+template <int DD>
+__global__ __launch_bounds__(256) void gmm_fit_labels_kernel(GmmFitArgs a, const int* labels) {
+  constexpr int LD = fit_pitch<DD>(), NJ = DD / 16, PANELS = DD / 64, STRIDE = DD * DD + DD + 1;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* xs = lds;                                            // FIT_TILE * LD
+  int* labs = reinterpret_cast<int*>(xs + FIT_TILE * LD);     // FIT_CHUNK
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, n16 = lane & 15;
+  const long long b_lo = (long long)blockIdx.x * a.per_block;
+  const long long b_hi = b_lo + a.per_block < a.n ? b_lo + a.per_block : a.n;
+  double* part = a.partials + (size_t)blockIdx.x * a.K * STRIDE;
+
+  for (long long c0 = b_lo; c0 < b_hi; c0 += FIT_CHUNK) {
+    const long long c1 = c0 + FIT_CHUNK < b_hi ? c0 + FIT_CHUNK : b_hi;
+    const int n_tiles = (int)((c1 - c0 + FIT_TILE - 1) / FIT_TILE);
+    const bool first = c0 == b_lo;
+    __syncthreads();  // (the previous chunk's readers are done)
+    for (int i = threadIdx.x; i < FIT_CHUNK; i += 256) labs[i] = c0 + i < c1 ? labels[c0 + i] : -1;
+    __syncthreads();
+
+    for (int k = 0; k < a.K; ++k) {
+      const float mu_f = gld(a.mu + (size_t)k * DD + threadIdx.x % DD);
+      double* dst = part + (size_t)k * STRIDE;
+      for (int panel = 0; panel < PANELS; ++panel) {
+        const int ib = 4 * panel + wave;
+        f64x4 acc[NJ];
+#pragma unroll
+        for (int jb = 0; jb < NJ; ++jb) acc[jb] = f64x4{0.0, 0.0, 0.0, 0.0};
+        double s0 = 0.0, s1 = 0.0;
+        bool present = false;
+        for (int t = 0; t < n_tiles; ++t) {
+          // (a barrier as well: the previous tile's readers are done)
+          if (!__syncthreads_or(threadIdx.x < FIT_TILE && labs[t * FIT_TILE + threadIdx.x] == k)) continue;
+          present = true;
+          fit_stage<DD>(xs, a.x, c0 + (long long)t * FIT_TILE, c1, mu_f);
+          __syncthreads();
+          const int* lt = labs + t * FIT_TILE + g;
+          const float* xg = xs + g * LD + n16;
+#pragma unroll 4
+          for (int s = 0; s < FIT_TILE / 4; ++s) {  // patches 4 s + g of the tile
+            const bool hit = lt[4 * s] == k;
+            const float* row = xg + 4 * s * LD;
+            const double av = hit ? (double)row[16 * ib] : 0.0;  // (selected, not multiplied: a patch that is not the
+            s0 += hit ? 1.0 : 0.0, s1 += av;                      //  component's may hold anything, NaN included)
+#pragma unroll
+            for (int jb = 0; jb < NJ; ++jb)
+              acc[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, hit ? (double)row[16 * jb] : 0.0, acc[jb], 0, 0, 0);
+          }
+        }
+        if (!first && !present) continue;  // (block-uniform: nothing to add)
+#pragma unroll
+        for (int jb = 0; jb < NJ; ++jb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            double* p = dst + (size_t)(16 * ib + g + 4 * r) * DD + 16 * jb + n16;
+            *p = first ? acc[jb][r] : *p + acc[jb][r];
+          }
+        const double t1 = fit_sum_lane_groups(s1), t0 = fit_sum_lane_groups(s0);
+        if (g == 0) {
+          double* p = dst + DD * DD + 16 * ib + n16;
+          *p = first ? t1 : *p + t1;
+        }
+        if (panel == 0 && threadIdx.x == 0) {
+          double* p = dst + DD * DD + DD;
+          *p = first ? t0 : *p + t0;
+        }
+      }
+    }
+  }
+  if (threadIdx.x == 0) a.lse_partials[blockIdx.x] = 0.0;
+}
+
 // out = [S0 (K) | S1 (K, D) | S2 (K, D, D) | L]: the blocks' partials added in block order in float64
 __global__ __launch_bounds__(256) void gmm_fit_reduce_kernel(const double* partials, const double* lse_partials, int blocks, int K,
                                                              int DD, double* out) {
@@ -312,13 +389,27 @@ extern "C" int jd_gmm_fit_destroy(jd_gmm_fit* fit) {
   return JD_OK;
 }
 
-extern "C" int jd_gmm_fit_step(jd_gmm_fit* fit, const float* x, long long n, const float* means, const float* prec_chol,
-                               const float* const_k, double* sums_out, void* stream) {
-  JD_REQUIRE(fit, "jd_gmm_fit_step: null handle");
-  JD_REQUIRE(x && means && prec_chol && const_k && sums_out, "jd_gmm_fit_step: null argument");
-  JD_REQUIRE(n >= 1 && n <= 2147483647LL / fit->D, "jd_gmm_fit_step: 1 <= n <= (2^31 - 1) / D, got n = %lld with D = %d", n, fit->D);
-  JD_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0, "jd_gmm_fit_step: x is not aligned to a float");
-  hipStream_t s = as_stream(stream);
+namespace jd {
+template <int DD>
+static int launch_fit_labels(const GmmFitArgs& a, const int* labels, unsigned blocks, hipStream_t s) {
+  const size_t lds = (size_t)(FIT_TILE * fit_pitch<DD>() + FIT_CHUNK) * sizeof(float);
+  static bool configured[64] = {};  // (per device: the attribute belongs to the device's copy of the kernel)
+  int dev = 0;
+  JD_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !configured[dev]) {
+    JD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gmm_fit_labels_kernel<DD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds));
+    if (dev >= 0 && dev < 64) configured[dev] = true;
+  }
+  gmm_fit_labels_kernel<DD><<<blocks, 256, lds, s>>>(a, labels);
+  JD_LAUNCH_CHECK();
+  return JD_OK;
+}
+}  // namespace jd
+
+// What the soft and the hard step share, so that the two cannot drift apart: the split of the patches into blocks with
+// the partial sums it needs (their layout is a contract between the step kernels and the reduce kernel), and the reduction.
+static int fit_split(jd_gmm_fit* fit, long long n, GmmFitArgs& a, unsigned& blocks_out) {
   const long long want = (n + FIT_BLOCK_MIN - 1) / FIT_BLOCK_MIN;
   long long blocks = std::min<long long>(want, fit->max_blocks);
   const long long per_block = ((n + blocks - 1) / blocks + FIT_TILE - 1) / FIT_TILE * FIT_TILE;
@@ -327,14 +418,50 @@ extern "C" int jd_gmm_fit_step(jd_gmm_fit* fit, const float* x, long long n, con
   int rc;
   if ((rc = fit->partials.reserve((size_t)blocks * fit->K * stride))) return rc;
   if ((rc = fit->lse_partials.reserve((size_t)blocks))) return rc;
-  GmmFitArgs a{};
-  a.x = x, a.mu = means, a.prec = prec_chol, a.const_k = const_k;
   a.partials = fit->partials.ptr, a.lse_partials = fit->lse_partials.ptr;
   a.n = n, a.per_block = per_block, a.K = fit->K;
-  if ((rc = fit->D == 64 ? launch_fit<64>(a, (unsigned)blocks, s) : launch_fit<256>(a, (unsigned)blocks, s))) return rc;
-  const size_t total = (size_t)fit->K * stride;
+  blocks_out = (unsigned)blocks;
+  return JD_OK;
+}
+
+static int fit_reduce(jd_gmm_fit* fit, unsigned blocks, double* sums_out, hipStream_t s) {
+  const size_t total = (size_t)fit->K * ((size_t)fit->D * fit->D + fit->D + 1);
   gmm_fit_reduce_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(fit->partials.ptr, fit->lse_partials.ptr, (int)blocks, fit->K,
                                                                          fit->D, sums_out);
   JD_LAUNCH_CHECK();
   return JD_OK;
+}
+
+extern "C" int jd_gmm_fit_step(jd_gmm_fit* fit, const float* x, long long n, const float* means, const float* prec_chol,
+                               const float* const_k, double* sums_out, void* stream) {
+  JD_REQUIRE(fit, "jd_gmm_fit_step: null handle");
+  JD_REQUIRE(x && means && prec_chol && const_k && sums_out, "jd_gmm_fit_step: null argument");
+  JD_REQUIRE(n >= 1 && n <= 2147483647LL / fit->D, "jd_gmm_fit_step: 1 <= n <= (2^31 - 1) / D, got n = %lld with D = %d", n, fit->D);
+  JD_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0, "jd_gmm_fit_step: x is not aligned to a float");
+  hipStream_t s = as_stream(stream);
+  GmmFitArgs a{};
+  unsigned blocks = 0;
+  int rc;
+  if ((rc = fit_split(fit, n, a, blocks))) return rc;
+  a.x = x, a.mu = means, a.prec = prec_chol, a.const_k = const_k;
+  if ((rc = fit->D == 64 ? launch_fit<64>(a, blocks, s) : launch_fit<256>(a, blocks, s))) return rc;
+  return fit_reduce(fit, blocks, sums_out, s);
+}
+
+extern "C" int jd_gmm_fit_step_labels(jd_gmm_fit* fit, const float* x, long long n, const float* means, const int* labels,
+                                      double* sums_out, void* stream) {
+  JD_REQUIRE(fit, "jd_gmm_fit_step_labels: null handle");
+  JD_REQUIRE(x && means && labels && sums_out, "jd_gmm_fit_step_labels: null argument");
+  JD_REQUIRE(n >= 1 && n <= 2147483647LL / fit->D, "jd_gmm_fit_step_labels: 1 <= n <= (2^31 - 1) / D, got n = %lld with D = %d", n,
+             fit->D);
+  JD_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(labels)) & 3) == 0,
+             "jd_gmm_fit_step_labels: x or labels is not aligned to 4 bytes");
+  hipStream_t s = as_stream(stream);
+  GmmFitArgs a{};
+  unsigned blocks = 0;
+  int rc;
+  if ((rc = fit_split(fit, n, a, blocks))) return rc;
+  a.x = x, a.mu = means;
+  if ((rc = fit->D == 64 ? launch_fit_labels<64>(a, labels, blocks, s) : launch_fit_labels<256>(a, labels, blocks, s))) return rc;
+  return fit_reduce(fit, blocks, sums_out, s);
 }

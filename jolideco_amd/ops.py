@@ -20,6 +20,7 @@ __all__ = [
     "ConvPlan",
     "GmmHandle",
     "GmmFitHandle",
+    "KMeansHandle",
     "ConvSameFunction",
     "PoissonNLLFunction",
     "GMMPatchPriorFunction",
@@ -936,3 +937,89 @@ class GmmFitHandle:
         s1 = flat[K:K + K * D].reshape(K, D).copy()
         s2 = flat[K + K * D:K + K * D + K * D * D].reshape(K, D, D).copy()
         return s0, s1, s2, float(flat[-1])
+
+    def step_labels(self, x, means, labels):
+        """The same sums for hard assignments r_nk = [labels[n] == k] (jd_gmm_fit_step_labels): ``labels`` is an int32
+        device tensor (n,); a label outside [0, K) contributes nothing.  Returns ``(sum r, sum r d, sum r d d^T)``."""
+        K, D = self.K, self.D
+        x = require_hip_tensor(x, "patches")
+        if x.ndim != 2 or x.shape[1] != D or not x.is_contiguous():
+            raise ValueError(f"patches must be a contiguous (n, {D}) tensor, got {tuple(x.shape)}")
+        require_hip_tensor(means, "means")
+        if tuple(means.shape) != (K, D) or not means.is_contiguous():
+            raise ValueError(f"means must be a contiguous {(K, D)} tensor, got {tuple(means.shape)}")
+        labels = _require_labels(labels, x.shape[0])
+        with torch.cuda.device(self.device):
+            check(_hip.lib().jd_gmm_fit_step_labels(self._handle, ptr(x), x.shape[0], ptr(means), c_void_p(labels.data_ptr()),
+                                                    c_void_p(self.sums.data_ptr()), stream_ptr(self.device)))
+            self._host.copy_(self.sums, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        flat = self._host.numpy()
+        s0 = flat[:K].copy()
+        s1 = flat[K:K + K * D].reshape(K, D).copy()
+        s2 = flat[K + K * D:K + K * D + K * D * D].reshape(K, D, D).copy()
+        return s0, s1, s2
+
+
+def _require_labels(labels, n):
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
+        raise RuntimeError("labels must be a HIP tensor (no CPU fallback)")
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
+        raise ValueError(f"labels must be a contiguous int32 ({n},) tensor, got {labels.dtype} {tuple(labels.shape)}")
+    return labels
+
+
+class KMeansHandle:
+    """Work space of the Lloyd step (jd_kmeans, csrc/kmeans.hip) for ``n_clusters`` centres over ``n_features`` = 64 or 256
+    features on one device.  ``max_blocks`` bounds the sets of partial sums (0: the default)."""
+
+    def __init__(self, n_features, n_clusters, device, max_blocks=0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("KMeansHandle needs a HIP device (no CPU fallback)")
+        self.D, self.K = int(n_features), int(n_clusters)
+        handle = c_void_p()
+        with torch.cuda.device(self.device):
+            check(_hip.lib().jd_kmeans_create(self.D, self.K, int(max_blocks), ctypes.byref(handle)))
+        self._handle = handle
+        size = self.K * (1 + self.D) + 3
+        self.sums = torch.empty(size, dtype=torch.float64, device=self.device)
+        self._host = torch.empty(size, dtype=torch.float64).pin_memory()
+
+    def close(self):
+        if self._handle is not None:
+            _hip.lib().jd_kmeans_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def launch(self, x, centres, labels):
+        """One Lloyd step on the current stream, without a copy or a synchronisation: ``labels`` is rewritten and
+        ``self.sums`` holds [count | sum x | inertia | changed | unassigned] once the stream has run."""
+        K, D = self.K, self.D
+        x = require_hip_tensor(x, "patches")
+        if x.ndim != 2 or x.shape[1] != D or not x.is_contiguous():
+            raise ValueError(f"patches must be a contiguous (n, {D}) tensor, got {tuple(x.shape)}")
+        require_hip_tensor(centres, "centres")
+        if tuple(centres.shape) != (K, D) or not centres.is_contiguous():
+            raise ValueError(f"centres must be a contiguous {(K, D)} tensor, got {tuple(centres.shape)}")
+        labels = _require_labels(labels, x.shape[0])
+        with torch.cuda.device(self.device):
+            check(_hip.lib().jd_kmeans_step(self._handle, ptr(x), x.shape[0], ptr(centres), c_void_p(labels.data_ptr()),
+                                            c_void_p(self.sums.data_ptr()), stream_ptr(self.device)))
+
+    def step(self, x, centres, labels):
+        """One Lloyd step over the patches ``x`` (n, D) for float32 device ``centres`` (K, D): ``labels`` (int32 device
+        tensor (n,)) is read -- for the count of changes -- and rewritten; returns float64 numpy ``(count (K,), sum x (K, D),
+        inertia, changed, unassigned)``; synchronises on the copy."""
+        K, D = self.K, self.D
+        self.launch(x, centres, labels)
+        with torch.cuda.device(self.device):
+            self._host.copy_(self.sums, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        flat = self._host.numpy()
+        return flat[:K].copy(), flat[K:K + K * D].reshape(K, D).copy(), float(flat[-3]), int(flat[-2]), int(flat[-1])

@@ -122,6 +122,31 @@ def random_start(patches, n_components, reg_covar=1e-6, random_state=0):
     return means, np.repeat(cov_all, n_components, axis=0), np.full(n_components, 1.0 / n_components)
 
 
+def kmeans_start(handle, patches, n_components, reg_covar=1e-6, random_state=0, max_iter=100, n_seed=None):
+    """The start of `GaussianMixtureModel.fit(init_params="kmeans")`: `kmeans` clusters the patches, ``handle``
+    (`ops.GmmFitHandle`) sums the moments of the hard assignments about the centres in one pass, and `em_m_step` turns
+    them into float64 (means, covariances + ``reg_covar`` I, weights) -- scikit-learn's start from one-hot
+    responsibilities.  The fourth result is the record `fit` keeps under ``fit_info["kmeans"]``."""
+    from .kmeans import kmeans
+
+    n, D = patches.shape
+    result = kmeans(patches, n_components, max_iter=max_iter, random_state=random_state, n_seed=n_seed)
+    if result.unassigned:
+        raise ValueError(f"{result.unassigned} patches hold non-finite values: the k-means start cannot place them")
+    starved = np.flatnonzero(~(result.counts >= D))
+    if starved.size:
+        raise ValueError(
+            f"component {int(starved[0])} is starved by the k-means start: its cluster holds {int(result.counts[starved[0]])} patches, "
+            f"fewer than the D = {D} patches a covariance needs (components {starved.tolist()}); choose fewer components or "
+            "another random_state"
+        )
+    s0, s1, s2 = handle.step_labels(patches, _upload(result.centres, patches.device), result.labels)
+    means, covariances, weights = em_m_step(result.centres, s0, s1, s2, n, reg_covar)
+    info = {"inertia": list(result.inertia), "n_iter": result.n_iter, "converged": result.converged, "counts": result.counts,
+            "means": means, "covariances": covariances, "weights": weights}
+    return means, covariances, weights, info
+
+
 _FIT_HANDLES = {}
 
 
@@ -235,7 +260,8 @@ class GaussianMixtureModel:
     # fitting -------------------------------------------------------------------------------
     @classmethod
     def fit(cls, patches, n_components=None, *, init=None, means_init=None, covariances_init=None, weights_init=None,
-            n_iter=100, tol=1e-3, reg_covar=1e-6, random_state=0, meta=None):
+            n_iter=100, tol=1e-3, reg_covar=1e-6, random_state=0, meta=None, init_params=None, kmeans_iter=100,
+            kmeans_seed_patches=None):
         """Fit a full-covariance mixture to ``patches`` by EM on the GPU, with the steps of
         ``sklearn.mixture.GaussianMixture(covariance_type="full")``.
 
@@ -243,8 +269,14 @@ class GaussianMixtureModel:
         The start is a model ``init``, or the three arrays ``means_init`` (K, D), ``covariances_init`` (K, D, D) and
         ``weights_init`` (K,), or -- with ``n_components`` alone -- K distinct patches drawn by
         ``numpy.random.RandomState(random_state)`` as means, the covariance of all patches + ``reg_covar`` I for every
-        component and uniform weights.  That start is deterministic; it is NOT scikit-learn's k-means start, so the
-        two packages agree step by step only from a common explicit start.
+        component and uniform weights (``init_params="random-patches"``, the default).  ``init_params="kmeans"`` is
+        scikit-learn's default scheme instead: `kmeans` clusters the patches (k-means++ seeds from
+        ``RandomState(random_state)`` on ``kmeans_seed_patches`` patches, at most ``kmeans_iter`` Lloyd steps on the device),
+        and the clusters' weights, means and covariances + ``reg_covar`` I -- one pass of hard assignments,
+        `jd_gmm_fit_step_labels`, finished by `em_m_step` -- start EM.  A cluster of fewer than D patches cannot carry a
+        covariance: ValueError.  Both starts are deterministic; neither draws scikit-learn's random numbers, so the two
+        packages agree step by step only from a common explicit start.  ``init_params`` cannot be combined with a given
+        start.
 
         Every step is one pass of the device over the patches (csrc/gmm_fit.hip: responsibilities, and the weighted
         moments about the current means); the division, the mean correction, the ridge and the Cholesky factors are done
@@ -253,10 +285,17 @@ class GaussianMixtureModel:
         covariance: ValueError names it.
 
         Returns a model built by `from_numpy` from the float64 result, carrying ``meta`` and a ``fit_info`` dict with
-        ``lower_bounds`` (one per step), ``converged``, ``n_iter`` and the float64 ``means``, ``covariances``, ``weights``."""
+        ``lower_bounds`` (one per step), ``converged``, ``n_iter`` and the float64 ``means``, ``covariances``, ``weights``;
+        after the k-means start also ``kmeans``: its ``inertia`` per Lloyd step, ``n_iter``, ``converged``, ``counts`` and
+        the start it produced (``means``, ``covariances``, ``weights``)."""
         from ...ops import GmmFitHandle
 
         given = [a is not None for a in (means_init, covariances_init, weights_init)]
+        if init_params is not None:
+            if init_params not in ("random-patches", "kmeans"):
+                raise ValueError(f'init_params is "random-patches" or "kmeans", got {init_params!r}')
+            if init is not None or any(given):
+                raise ValueError("init_params selects a start of its own: it cannot be given with `init` or *_init arrays")
         if init is not None and any(given):
             raise ValueError("give either `init` or means_init / covariances_init / weights_init, not both")
         if any(given) and not all(given):
@@ -301,10 +340,14 @@ class GaussianMixtureModel:
         patches = patches.contiguous()
         device = patches.device
 
-        if means is None:
+        handle = _fit_handle(GmmFitHandle, device, D, K)
+        kmeans_info = None
+        if means is None and init_params == "kmeans":
+            means, covariances, weights, kmeans_info = kmeans_start(handle, patches, K, reg_covar, random_state, kmeans_iter,
+                                                                    kmeans_seed_patches)
+        elif means is None:
             means, covariances, weights = random_start(patches, K, reg_covar, random_state)
 
-        handle = _fit_handle(GmmFitHandle, device, D, K)
         lower_bounds, converged = [], False
         previous = -np.inf
         for _ in range(int(n_iter)):
@@ -324,6 +367,8 @@ class GaussianMixtureModel:
         # (the float64 parameters as well: the model's own arrays are their float32 roundings)
         model.fit_info = {"lower_bounds": lower_bounds, "converged": converged, "n_iter": len(lower_bounds),
                           "means": means, "covariances": covariances, "weights": weights}
+        if kmeans_info is not None:
+            model.fit_info["kmeans"] = kmeans_info
         return model
 
     @classmethod
