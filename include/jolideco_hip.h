@@ -123,6 +123,18 @@ int jd_conv_plan_takes_walk(const jd_conv_plan* plan, int n_datasets);
  *             2 the FFT launches dataset by dataset and the tail over all
  *   [7]       transposed shift: R = 1, 2, 4 rows per thread of the four-pixel kernel (16-byte aligned images), 0 scalar kernels */
 int jd_conv_plan_step_route(const jd_conv_plan* plan, int upsampling, int n_datasets, int32_t* route8);
+/* Which kernels a plain convolution, its adjoint and the un-up-sampled likelihood step launch on a plan of the native FFT
+ * path -- asked of the function the column launch itself asks for its table entry, and of the row launches' schedule
+ * function; read-only, no device work; JD_ERR_INVALID for any other plan.  route8 =
+ *   [0], [1]  Nx, Ny: lengths of the row / column transforms
+ *   [2]       lanes (threads) per column: 64, 128 or 256
+ *   [3]       columns per block actually launched (option JD_FFT_NATIVE = 2 / 4 / 8 forces it where the table entry that
+ *             leads to can be launched with lanes x columns threads; otherwise the default stands)
+ *   [4]       1: a compile-time entry of the column table, 0: the generic kernel of that many lanes
+ *   [5]       row schedule (numbered as in jd_conv_plan_step_route) of a forward-row launch over `n_datasets` datasets
+ *   [6]       row schedule of the single-image inverse-row launch
+ *   [7]       0 (reserved) */
+int jd_conv_plan_fft_route(const jd_conv_plan* plan, int n_datasets, int32_t* route8);
 /* Which instantiation of the MFMA Toeplitz kernel (csrc/directconv.hip) a DIRECT plan launches -- computed by the functions
  * the launch itself calls, from the plan's own fields; read-only, no device work; an error for a plan of another method.
  * kernel4 =

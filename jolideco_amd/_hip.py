@@ -40,6 +40,7 @@ EXPORTS = {
     "jd_conv_native_fft_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "jd_conv_plan_takes_walk": (c_int, [c_void_p, c_int]),
     "jd_conv_plan_step_route": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32)]),
+    "jd_conv_plan_fft_route": (c_int, [c_void_p, c_int, POINTER(c_int32)]),
     "jd_conv_plan_direct_kernel": (c_int, [c_void_p, POINTER(c_int32)]),
     "jd_conv_operator_walk_frame": (c_int, [c_void_p, c_void_p]),
     "jd_conv_operator_forget": (c_int, [c_void_p]),

@@ -928,6 +928,17 @@ extern "C" int jd_conv_plan_step_route(const jd_conv_plan* p, int upsampling, in
   return JD_OK;
 }
 
+extern "C" int jd_conv_plan_fft_route(const jd_conv_plan* p, int n_datasets, int32_t* route8) {
+  JD_REQUIRE(p && route8, "jd_conv_plan_fft_route: null argument");
+  JD_REQUIRE(n_datasets >= 1, "jd_conv_plan_fft_route: n_datasets = %d", n_datasets);
+  JD_REQUIRE(p->method == JD_CONV_FFT && p->native, "jd_conv_plan_fft_route: not a plan of the native FFT path");
+  int fft[7] = {0, 0, 0, 0, 0, -1, -1};
+  if (int rc = fftn_fft_route(p->fftn, n_datasets, fft)) return rc;
+  for (int i = 0; i < 7; ++i) route8[i] = fft[i];
+  route8[7] = 0;
+  return JD_OK;
+}
+
 extern "C" int jd_conv_plan_direct_kernel(const jd_conv_plan* p, int32_t* kernel4) {
   JD_REQUIRE(p && kernel4, "jd_conv_plan_direct_kernel: null argument");
   JD_REQUIRE(p->method == JD_CONV_DIRECT, "jd_conv_plan_direct_kernel: not a plan of the direct method");

@@ -582,8 +582,12 @@ __device__ __forceinline__ void column_conv_static(float2* x, const float2* tw, 
   column_pass_inplace<R0, 1, ceil_div(N / R0, LANES), LANES, POW2, lin_in(N, R0), lin_out(R0, R2 * R1)>(x, N, R2 * R1, tw, lane);
 }
 
+// threads per block an instantiation is compiled for (its __launch_bounds__, and the `max_threads` of its entry in the
+// table of cols_choice): the generic form (CBS = 0) takes its columns per block from blockDim, up to 512 threads
+constexpr int cols_max_threads(int LANES, int CBS) { return LANES * CBS > 512 ? 1024 : 512; }
+
 template <int LANES, int CBS, int R0, int R1, int R2>
-__global__ __launch_bounds__((LANES * CBS > 512 ? 1024 : 512), (LANES * CBS > 512 ? 4 : LANES == 256 ? JD_COLS256_WAVES : 3)) void fftn_cols_kernel(ColsArgs a) {
+__global__ __launch_bounds__((cols_max_threads(LANES, CBS)), (LANES * CBS > 512 ? 4 : LANES == 256 ? JD_COLS256_WAVES : 3)) void fftn_cols_kernel(ColsArgs a) {
   extern __shared__ float2 lds[];
   constexpr bool STATIC = R0 > 0;
   const int tid = threadIdx.x, lane = tid % LANES, wc = tid / LANES, CB = STATIC ? CBS : (int)blockDim.x / LANES;
@@ -1305,6 +1309,81 @@ int lds_attr(const void* kernel, size_t bytes) {
   return JD_OK;
 }
 
+// The column kernel of a plan: lanes per column, columns per block and the table entry -- asked by the launch (launch_cols)
+// and by the route query (fftn_fft_route).
+using ColsKernel = void (*)(ColsArgs);
+struct ColsEntry {
+  int lanes, cb, r0, r1, r2;  // r0 = 0: the generic form, any schedule and any cb
+  ColsKernel kernel;
+  int max_threads;  // the kernel's __launch_bounds__: a (lanes, cb) beyond it is never launched
+};
+#define JD_COLS_ENTRY(L, CB, R0, R1, R2) {L, CB, R0, R1, R2, fftn_cols_kernel<L, CB, R0, R1, R2>, cols_max_threads(L, CB)}
+const ColsEntry COLS_TABLE[] = {
+    JD_COLS_ENTRY(64, 4, 16, 8, 9),     // 1152: 2048-row images, PSFs up to 129 rows
+    JD_COLS_ENTRY(64, 8, 16, 8, 9),     // (default there: 64-byte pieces, two blocks of 512 threads per CU)
+    JD_COLS_ENTRY(128, 2, 16, 16, 9),   // 2304: 4096-row images
+    JD_COLS_ENTRY(128, 4, 16, 16, 9),   // (default: four columns per block, 32-byte pieces)
+    JD_COLS_ENTRY(128, 8, 16, 16, 9),   // (JD_FFT_NATIVE=8: one block of 1024 threads per CU, 64-byte pieces)
+    JD_COLS_ENTRY(64, 4, 16, 8, 8),     // 1024
+    JD_COLS_ENTRY(128, 2, 16, 16, 8),   // 2048
+    JD_COLS_ENTRY(128, 4, 16, 16, 8),
+    JD_COLS_ENTRY(64, 4, 8, 8, 9),      // 576: 1024-row images
+    JD_COLS_ENTRY(64, 4, 8, 8, 8),      // 512
+    JD_COLS_ENTRY(64, 0, 0, 0, 0),      // generic
+    // (no generic two-wave form: 2048 and 2304 are the only lengths on 128 lanes, and the entries above cover every number
+    // of columns a 512-thread block holds of them)
+    JD_COLS_ENTRY(256, 0, 0, 0, 0),     // 4096 and 4608: images beyond 4600 rows, two columns per block
+};
+#undef JD_COLS_ENTRY
+
+struct ColsChoice {
+  int lanes = 0, cb = 0;
+  const ColsEntry* entry = nullptr;  // null: no column kernel for this length
+};
+
+// the entry that runs `cb` columns per block of this schedule: its compile-time form if the table has one, else the generic
+// form of that many lanes
+const ColsEntry* cols_entry(const FftPasses& fy, int lanes, int cb) {
+  for (const ColsEntry& t : COLS_TABLE) {
+    const bool is_static = t.r0 && fy.n == 3 && t.r0 == fy.r[0] && t.r1 == fy.r[1] && t.r2 == fy.r[2] && t.cb == cb;
+    if (t.lanes == lanes && (is_static || !t.r0)) return &t;
+  }
+  return nullptr;
+}
+
+ColsChoice cols_choice(const FftNative& n) {
+  const FftPasses fy = passes_of(n.Ny);
+  ColsChoice c;
+  c.lanes = column_lanes(n.Ny, fy);
+  if (!c.lanes) return c;
+  const int lanes = c.lanes;
+  const size_t per_col = (size_t)lp_size(n.Ny) * sizeof(float2);
+  // columns per block: 4 (32 contiguous bytes of every spectrum row).  Measured at 2048^2, Ny = 1152 (round 4, one-wave
+  // columns): 4 columns 24.2 us, 3 columns (768 blocks = 3 per CU, 24-byte pieces) 26.7, 9 columns (one block per CU) 25.9.
+  // Two-wave columns (Ny = 2304: 4096-row images): with the round-5 kernels (packed arithmetic, linear LDS indices: 110
+  // registers, two blocks of 512 threads per CU) 4 columns 74.8 against 87.0 us for 2 (c6; round 4, 139 registers: 104
+  // against 91).  The four-wave columns (generic kernel, 4096 and 4608 points) keep 2: 512 threads.
+  // One-wave columns of 2048-row images (Ny = 1152), round 5: 8 columns per block (64-byte pieces, two blocks of 512 threads
+  // per CU) 117 against 133 us for 4 per launch over 8 observations (c3 through the FFT path).
+  const bool static_two_wave = lanes == 128 && fy.n == 3 && fy.r[0] == 16 && fy.r[1] == 16 && (fy.r[2] == 9 || fy.r[2] == 8);
+  const bool static_1152 = lanes == 64 && fy.n == 3 && fy.r[0] == 16 && fy.r[1] == 8 && fy.r[2] == 9;
+  int cb = static_1152 ? 8 : lanes == 64 || static_two_wave ? 4 : 2;
+  while (cb > 2 && n.Nx % cb != 0) cb /= 2;
+  // the kernel of the schedule: compile-time forms for the lengths of the usual image sizes (default columns per block),
+  // the generic form for everything else
+  c.cb = cb, c.entry = cols_entry(fy, lanes, cb);
+  // (tuning: JD_FFT_NATIVE = 2 / 4 / 8 forces the columns per block -- where the entry that leads to can be launched with
+  // that many threads: two-wave columns x 8 without a compile-time form would be 1024 threads on the generic kernel, which
+  // is compiled for 512; the default stands there)
+  const int ocb = opt_value(OPT_FFT_NATIVE, 1);
+  if ((ocb == 2 || ocb == 4 || ocb == 8) && (size_t)ocb * per_col <= 160 * 1024 && n.Nx % ocb == 0 && (lanes < 256 || ocb == 2)) {
+    const ColsEntry* forced = cols_entry(fy, lanes, ocb);
+    if (forced && ocb * lanes <= forced->max_threads) c.cb = ocb, c.entry = forced;
+  }
+  if (c.entry && c.cb * lanes > c.entry->max_threads) c.entry = nullptr;  // (no default reaches this)
+  return c;
+}
+
 int launch_cols(const FftNative& n, const float2* khat, int adjoint, hipStream_t stream, const FftBatch* batch = nullptr, int n_batch = 0,
                 int d0 = 0, int pool = 1) {
   const FftPasses fy = passes_of(n.Ny);
@@ -1315,53 +1394,14 @@ int launch_cols(const FftNative& n, const float2* khat, int adjoint, hipStream_t
   a.batch = batch, a.n_batch = n_batch, a.d0 = d0;
   a.pool_out = adjoint ? 1 : pool, a.pool_in = adjoint ? pool : 1;
   const size_t per_col = (size_t)lp_size(n.Ny) * sizeof(float2);
-  const int lanes = column_lanes(n.Ny, fy);
-  if (!lanes) return fail(JD_ERR_INVALID, "native FFT: no column kernel for length %d", n.Ny);
-  // columns per block: 4 (32 contiguous bytes of every spectrum row).  Measured at 2048^2, Ny = 1152 (round 4, one-wave
-  // columns): 4 columns 24.2 us, 3 columns (768 blocks = 3 per CU, 24-byte pieces) 26.7, 9 columns (one block per CU) 25.9.
-  // Two-wave columns (Ny = 2304: 4096-row images): with the round-5 kernels (packed arithmetic, linear LDS indices: 110
-  // registers, two blocks of 512 threads per CU) 4 columns 74.8 against 87.0 us for 2 (c6; round 4, 139 registers: 104
-  // against 91).  The generic two-wave kernel (168 registers) keeps 2.
-  // One-wave columns of 2048-row images (Ny = 1152), round 5: 8 columns per block (64-byte pieces, two blocks of 512 threads
-  // per CU) 117 against 133 us for 4 per launch over 8 observations (c3 through the FFT path).
-  const bool static_two_wave = lanes == 128 && fy.n == 3 && fy.r[0] == 16 && fy.r[1] == 16 && (fy.r[2] == 9 || fy.r[2] == 8);
-  const bool static_1152 = lanes == 64 && fy.n == 3 && fy.r[0] == 16 && fy.r[1] == 8 && fy.r[2] == 9;
-  int cb = static_1152 ? 8 : lanes == 64 || static_two_wave ? 4 : 2;
-  while (cb > 2 && n.Nx % cb != 0) cb /= 2;
-  const int ocb = opt_value(OPT_FFT_NATIVE, 1);  // (tuning: JD_FFT_NATIVE = 2 / 4 / 8 forces the columns per block)
-  if ((ocb == 2 || ocb == 4 || ocb == 8) && (size_t)ocb * per_col <= 160 * 1024 && n.Nx % ocb == 0 && ocb * lanes <= 1024 && (lanes < 256 || ocb == 2)) cb = ocb;
+  const ColsChoice c = cols_choice(n);
+  if (!c.entry) return fail(JD_ERR_INVALID, "native FFT: no column kernel for length %d", n.Ny);
+  const int lanes = c.lanes, cb = c.cb;
   a.groups = n.Nx / cb;
-  // the kernel of the schedule: compile-time forms for the lengths of the usual image sizes (default columns per block),
-  // the generic form for everything else
-  using Kernel = void (*)(ColsArgs);
-  struct Entry {
-    int lanes, cb, r0, r1, r2;
-    Kernel kernel;
-  };
-  static Entry table[] = {
-      {64, 4, 16, 8, 9, fftn_cols_kernel<64, 4, 16, 8, 9>},    // 1152: 2048-row images, PSFs up to 129 rows
-      {64, 8, 16, 8, 9, fftn_cols_kernel<64, 8, 16, 8, 9>},    // (default there: 64-byte pieces, two blocks of 512 threads per CU)
-      {128, 2, 16, 16, 9, fftn_cols_kernel<128, 2, 16, 16, 9>},  // 2304: 4096-row images
-      {128, 4, 16, 16, 9, fftn_cols_kernel<128, 4, 16, 16, 9>},  // (default: four columns per block, 32-byte pieces)
-      {128, 8, 16, 16, 9, fftn_cols_kernel<128, 8, 16, 16, 9>},  // (JD_FFT_NATIVE=8: one block of 1024 threads per CU, 64-byte pieces)
-      {64, 4, 16, 8, 8, fftn_cols_kernel<64, 4, 16, 8, 8>},    // 1024
-      {128, 2, 16, 16, 8, fftn_cols_kernel<128, 2, 16, 16, 8>},  // 2048
-      {128, 4, 16, 16, 8, fftn_cols_kernel<128, 4, 16, 16, 8>},
-      {64, 4, 8, 8, 9, fftn_cols_kernel<64, 4, 8, 8, 9>},      // 576: 1024-row images
-      {64, 4, 8, 8, 8, fftn_cols_kernel<64, 4, 8, 8, 8>},      // 512
-      {64, 0, 0, 0, 0, fftn_cols_kernel<64, 0, 0, 0, 0>},      // generic
-      {128, 0, 0, 0, 0, fftn_cols_kernel<128, 0, 0, 0, 0>},
-      {256, 0, 0, 0, 0, fftn_cols_kernel<256, 0, 0, 0, 0>},    // 4096 and 4608: images beyond 4600 rows, two columns per block
-  };
-  Entry* e = nullptr;
-  for (Entry& t : table) {
-    const bool is_static = t.r0 && fy.n == 3 && t.r0 == fy.r[0] && t.r1 == fy.r[1] && t.r2 == fy.r[2] && t.cb == cb;
-    if (t.lanes == lanes && (is_static || !t.r0) && !e) e = &t;
-  }
-  int rc = lds_attr(reinterpret_cast<const void*>(e->kernel), cb * per_col);
+  int rc = lds_attr(reinterpret_cast<const void*>(c.entry->kernel), cb * per_col);
   if (rc) return rc;
   ProfScope prof(JD_KERNEL_CMUL, stream);
-  hipLaunchKernelGGL(e->kernel, dim3(((a.groups + 7) / 8) * 8 * (n_batch ? n_batch : 1)), dim3(lanes * cb), cb * per_col, stream, a);
+  hipLaunchKernelGGL(c.entry->kernel, dim3(((a.groups + 7) / 8) * 8 * (n_batch ? n_batch : 1)), dim3(lanes * cb), cb * per_col, stream, a);
   JD_LAUNCH_CHECK();
   return JD_OK;
 }
@@ -1627,6 +1667,20 @@ void fftn_step_route(const FftNative& n, int upsampling, int per_launch, int* ro
   route6[3] = pooled ? row_schedule(f, n.Nx, n.W, n.Hh / upsampling * per_launch) : -1;
   route6[4] = pooled ? 1 : 0;
   route6[5] = pooled && pooled_column_io(n, upsampling) > 1 ? 1 : 0;
+}
+
+// The kernels a plain convolution / adjoint and the un-up-sampled likelihood step launch (jd_conv_plan_fft_route): route7 =
+// {Nx, Ny, lanes per column, columns per block, 1 for a compile-time column entry, row schedule of a forward-row launch
+// over `n_datasets` datasets, row schedule of the single-image inverse launch} -- asked of the functions the launches ask.
+int fftn_fft_route(const FftNative& n, int n_datasets, int* route7) {
+  const ColsChoice c = cols_choice(n);
+  if (!c.entry) return fail(JD_ERR_INVALID, "native FFT: no column kernel for length %d", n.Ny);
+  const FftPasses f = passes_of(n.Nx);
+  route7[0] = n.Nx, route7[1] = n.Ny;
+  route7[2] = c.lanes, route7[3] = c.cb, route7[4] = c.entry->r0 ? 1 : 0;
+  route7[5] = row_schedule(f, n.Nx, n.W, n.Hh * (n_datasets > 1 ? n_datasets : 1));
+  route7[6] = row_schedule(f, n.Nx, n.W, n.Hh);
+  return JD_OK;
 }
 
 }  // namespace jd

@@ -303,6 +303,7 @@ int fftn_poisson_step_pooled_batch(const FftNative& n, int upsampling, int nd, c
                                    double norm_grad_scale, int sequential);
 bool fftn_pooled_supported(const FftNative& n, int upsampling);
 void fftn_step_route(const FftNative& n, int upsampling, int per_launch, int* route6);
+int fftn_fft_route(const FftNative& n, int n_datasets, int* route7);
 int fftn_poisson_step_pooled(const FftNative& n, int upsampling, const float* flux, const float* exposure, const float2* khat,
                              const float* background, const float* counts, const float* log_bkg_norm, double* partials,
                              double* partials_b, float eps, float inv_n, float* target, float coef, int accumulate,

@@ -170,6 +170,19 @@ class ConvPlan:
             "shift_bwd_rows": int(out[7]),
         }
 
+    def fft_route(self, n_datasets=1):
+        """The kernels a plain convolution, its adjoint and the un-up-sampled likelihood step launch on a native FFT plan
+        (jd_conv_plan_fft_route; an error for any other plan): dict of ``Nx``, ``Ny``, ``col_lanes`` (threads per column),
+        ``col_block`` (columns per block launched), ``col_static`` (1: a compile-time entry of the column table, 0: the
+        generic kernel), ``rows_fwd`` (name of `ROW_SCHEDULES` of a forward-row launch over ``n_datasets`` datasets) and
+        ``rows_inv`` (of the single-image inverse-row launch)."""
+        out = (ctypes.c_int32 * 8)()
+        check(_hip.lib().jd_conv_plan_fft_route(self._handle, int(n_datasets), out))
+        return {
+            "Nx": int(out[0]), "Ny": int(out[1]), "col_lanes": int(out[2]), "col_block": int(out[3]),
+            "col_static": int(out[4]), "rows_fwd": self.ROW_SCHEDULES[out[5]], "rows_inv": self.ROW_SCHEDULES[out[6]],
+        }
+
     def direct_kernel(self):
         """The instantiation of the MFMA Toeplitz kernel a "direct" plan launches (jd_conv_plan_direct_kernel): dict of
         ``KC`` (fp32: 16 .. 48, split: 32 or 64), ``split`` (the split-fp16 kernel, not the fp32 one) and ``vec_fwd`` /

@@ -73,6 +73,8 @@ def test_argument_validation_reports_errors(lib):
     route = (ctypes.c_int32 * 8)()
     assert lib.jd_conv_plan_step_route(None, 2, 1, route) == -1
     assert b"null argument" in lib.jd_last_error()
+    assert lib.jd_conv_plan_fft_route(None, 1, route) == -1
+    assert b"jd_conv_plan_fft_route: null argument" in lib.jd_last_error()
     total, count = ctypes.c_double(), ctypes.c_longlong()
     assert lib.jd_profile_read(99, ctypes.byref(total), ctypes.byref(count)) == -1
     # the band sum's fused step takes no addend images (non-null dummy pointers: the call returns before it looks at them)

@@ -24,7 +24,7 @@ for name in _missing:  # (a parent that has the entries runs as it is: the wrapp
     _hip.EXPORTS.pop(name)
 if _missing:
     core.FitSession._likelihood_addends = lambda self, early: None
-for name in ("jd_conv_plan_direct_kernel",):  # queries that only tests ask: a library without them runs the same steps
+for name in ("jd_conv_plan_direct_kernel", "jd_conv_plan_fft_route"):  # queries that only tests ask: a library without them runs the same steps
     if not hasattr(_lib, name):
         _hip.EXPORTS.pop(name)
 sys.argv = [os.path.join(ROOT, "bench.py")] + sys.argv[1:]
