@@ -463,6 +463,30 @@ int jd_gmm_prior_fwd_bwd_step(jd_gmm* gmm, const float* flux, int H, int W, int 
                               int marginalize, float value_scale, float* value_out, int accumulate_value,
                               float grad_coef, const jd_step* step, const int* shift_dev, int phases, void* stream);
 
+/* The same prior with `cycle_spin_subpix=True` (priors/patches/core.py:189-246; utils/torch.py:31-38,91-143): the patches
+ * are cut from s = conv2d(roll(n(flux), (shift_y, shift_x)), k, padding="same"), the 3 x 3 cross-correlation of the rolled,
+ * normed image with k[i][j] = wy(i - 1) * wx(j - 1), w(t) = 1 - |t - o| where |t - o| < 1, else 0 (o = x0 for columns, y0
+ * for rows, both in [-0.5, 0.5]; the weights are formed in float32 as the reference's `grid_weights` does), ZERO outside
+ * the rolled image.  Two streaming kernels around the unchanged pass: with (Y, X) = ((y + shift_y) mod H, (x + shift_x)
+ * mod W) the rolled position of pixel (y, x), the first writes the staged image in the un-rolled frame,
+ *   S[y, x] = sum_{a,b in {-1,0,1}} k[a+1][b+1] n[(y+a) mod H, (x+b) mod W] [0 <= Y+a < H] [0 <= X+b < W]
+ * (the stencil wraps around the image except across the seam the roll puts at row H - shift_y and column W - shift_x, where
+ * the tap is dropped); jd_gmm_prior_fwd_bwd then runs on S with the identity norm, the handle's patch norm and the same
+ * roll, its gradient G = grad_coef * d(sum v_patch)/dS going to a zeroed image of the handle; the second adds
+ *   dflux[y, x] = n'(flux[y, x]) sum_{a,b} k[a+1][b+1] G[(y-a) mod H, (x-b) mod W] [0 <= Y-a < H] [0 <= X-b < W]
+ * to grad_flux_accum (a pixel whose sum is exactly 0 receives nothing, as in the gather).  No atomics, the nine additions
+ * in row-major (a, b) order: run-to-run identical.  grad_flux_accum == NULL: value (and arg-max) only.  Value, arg-max,
+ * marginalize, the image norm and the patch norm of the handle (left as found) mean what they mean for
+ * jd_gmm_prior_fwd_bwd; with x0 = y0 = 0 the result is that call's, bit for bit.  The WHOLE prior only (no patch row shard,
+ * no band, no phases, no fused optimizer step); D = 64 and D = 256 handles.
+ * shift_dev (nullable): device [2] = roll residues in [0, H) x [0, W), read instead of shift_y / shift_x; offset_dev
+ * (nullable): device [2] = {x0, y0}, read instead of x0 / y0 (captured epochs).  By-value offsets that are not finite or
+ * outside [-0.5, 0.5], a NULL flux or value_out, an image smaller than a patch: JD_ERR_INVALID, nothing is launched. */
+int jd_gmm_prior_subpix_fwd_bwd(jd_gmm* gmm, const float* flux, int H, int W, int stride, int shift_y, int shift_x,
+                                float x0, float y0, int marginalize, float value_scale, float* value_out,
+                                int accumulate_value, float grad_coef, float* grad_flux_accum, int32_t* argmax_out,
+                                const int* shift_dev, const float* offset_dev, void* stream);
+
 /* Diagnostics of the screened arg-max path, read without synchronisation from host-mapped memory the last block of a
  * pass writes: out[0..4] = {generation of the last finished pass, it fell back to the dense fp32 kernel (0 / 1), bucket
  * slots its surviving records used, patches it covered, gradient rows per patch the record buffer has room for now}.

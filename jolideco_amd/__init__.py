@@ -22,6 +22,7 @@ from .priors import (
     MultiScalePrior,
     Priors,
     SmoothnessPrior,
+    SubpixelGMMPatchPrior,
     UniformPrior,
 )
 
@@ -43,6 +44,7 @@ __all__ = [
     "GaussianMixtureModel",
     "GMMPatchPrior",
     "MultiScalePrior",
+    "SubpixelGMMPatchPrior",
     "UniformPrior",
     "InverseGammaPrior",
     "ExponentialPrior",

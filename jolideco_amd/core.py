@@ -659,6 +659,10 @@ class FitSession:
         multiscale = [name for name, c in components.items() if getattr(getattr(c, "prior", None), "shift_kind", None) == "levels"]
         # (a draw of a multi-scale prior is one pair per level, on grids of different sizes: by-value epochs only)
         self.has_multiscale = bool(multiscale)
+        # (a draw of a patch prior with a sub-pixel cycle spin is a roll AND two offsets: a planned epoch would need a
+        # four-word slot per evaluation -- by-value epochs only)
+        self.has_subpix_patches = any(getattr(getattr(c, "prior", None), "shift_kind", None) == "roll+subpixel"
+                                      for c in components.values())
         if multiscale and deconvolver.checkpoint_path is not None:
             prior = components[multiscale[0]].prior
             raise NotImplementedError(
@@ -790,7 +794,7 @@ class FitSession:
         if getattr(deconvolver, "use_graph", None) is not None:
             self.graph_mode = "always" if deconvolver.use_graph else "never"
         self.use_graph = self.graph_mode == "always"
-        self.graph_policy = {"always": "captured epochs (forced)", "never": "no capture (forced)"}.get(self.graph_mode, "undecided")
+        self.graph_policy = {"always": "captured epochs (forced)", "never": "no capture (forced)"}.get(self.graph_mode, self._open_policy())
         self._probe = []  # (host seconds, start event, end event) of the by-value probe epochs
         self._trial = None  # the replayed epochs being timed against them
         # the GMM prior's first phase on a second stream beside the likelihood launches (`_start_priors`)
@@ -973,19 +977,27 @@ class FitSession:
         self._option_generation = _hip.OPTION_GENERATION
         self._trial = None
         if self.graph_mode == "auto":
-            self.use_graph, self.graph_policy, self._probe = False, "undecided", []
+            self.use_graph, self.graph_policy, self._probe = False, self._open_policy(), []
             if self.overlap_mode == "auto":
                 self.overlap_prior = True
+
+    def _open_policy(self):
+        """`graph_policy` of the "auto" mode before anything is measured: "undecided" -- or, for a session that can only run
+        by-value epochs because of a patch prior with a sub-pixel cycle spin, that fact (nothing will be measured)."""
+        if getattr(self, "has_subpix_patches", False):
+            return "by value (a SubpixelGMMPatchPrior draws a roll and two offsets per evaluation: no planned epochs)"
+        return "undecided"
 
     def _planned_capable(self):
         """Planned epochs apply: one process, the session's own optimizer step (a hook sees every gradient through the
         by-value path), no event brackets around collectives, no kernel timers, no sparse component (its stepper takes
         its bias terms by value: by-value epochs only, nothing is captured) and no multi-scale prior (a draw is one pair
-        per level on grids of different sizes: a captured epoch would bake them in).  The options of torch.optim keep
+        per level on grids of different sizes: a captured epoch would bake them in) and no patch prior with a sub-pixel
+        cycle spin (its draw is a roll and two offsets; the two-word slots hold one or the other).  The options of torch.optim keep
         planned and captured epochs -- `jd_optimizer_step` reads the bias terms from device memory like the fused steps --
         except a momentum (SGD): the first step of a parameter makes the buffer the gradient, later ones read it, and a
         replayed launch cannot know which it is; a session with ``momentum != 0`` runs by-value epochs only."""
-        if self.has_sparse or getattr(self, "has_multiscale", False):
+        if self.has_sparse or getattr(self, "has_multiscale", False) or getattr(self, "has_subpix_patches", False):
             return False
         cfg = self.cfg
         if optimizer_options(cfg)[0].get("momentum"):

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "jd_common.h"
+#include "jd_subpix.h"
 #include "kernels.h"
 
 namespace jd {
@@ -704,22 +705,7 @@ struct SubpixArgs {
   int kind, H, W;
 };
 
-// k[i][j] = wx(j - 1) * wy(i - 1), w(t) = 1 - |t - o| where |t - o| < 1, else 0: the float32 operations of
-// `grid_weights`, one by one (no contraction), so the weights carry the reference's bits
-__device__ __forceinline__ void subpix_weights(float x0, float y0, float (&k)[3][3]) {
-#pragma clang fp contract(off)
-  float wx[3], wy[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const float dx = fabsf((float)(t - 1) - x0), dy = fabsf((float)(t - 1) - y0);
-    wx[t] = dx < 1.f ? 1.f - dx : 0.f;
-    wy[t] = dy < 1.f ? 1.f - dy : 0.f;
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) k[i][j] = wx[j] * wy[i];
-}
+// (the nine weights k[i][j] = wx(j - 1) * wy(i - 1): `subpix_weights` of jd_subpix.h, shared with the GMM patch prior)
 
 // VEC: W % 4 == 0 and 16-byte aligned images -- the 64 columns of the tile go in 16-byte loads, the read-modify-write of
 // grad in 16-byte loads and stores (a group of 4 columns is then inside the image or outside as a whole)

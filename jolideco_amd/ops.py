@@ -474,11 +474,13 @@ class GmmHandle:
 
     def prior_fwd_bwd(self, flux, stride, shifts, value_out, value_scale, grad=None, grad_coef=0.0,
                       marginalize=False, patch_rows=(0, -1), accumulate_value=False, argmax_out=None, band_out=None, phases=3,
-                      norm=None, patch_norm=None):
+                      norm=None, patch_norm=None, subpix=None):
         """``band_out``: instead of accumulating into ``grad``, write the gradient of the patch rows ``patch_rows`` as the
         band of the rolled frame they cover (jd_gmm_prior_band_fwd_bwd; `band_rows` gives its extent).
         ``norm``: the prior's image norm (None = identity); the gradient is the one with respect to the raw flux.
-        ``patch_norm``: the prior's patch norm (None = subtract-mean)."""
+        ``patch_norm``: the prior's patch norm (None = subtract-mean).
+        ``subpix``: the offsets (x0, y0) of a sub-pixel cycle spin -- or a `DeviceShifts` whose ``dev`` holds them as two
+        float32 in device memory -- applied behind the roll (jd_gmm_prior_subpix_fwd_bwd): the whole prior only."""
         flux = require_hip_tensor(flux, "flux")
         self.set_image_norm(norm)
         self.set_patch_norm(patch_norm)
@@ -491,6 +493,21 @@ class GmmHandle:
                 raise ValueError("device-resident shifts are not available for the band form")
             shift_dev, shifts = ptr(shifts.dev), shifts.host
         sy, sx = (0, 0) if shifts is None else shifts
+        if subpix is not None:
+            if band_out is not None or phases != 3 or tuple(patch_rows) != (0, -1):
+                raise ValueError("a sub-pixel cycle spin evaluates the whole prior: no patch_rows, band_out or phases")
+            offset_dev = None
+            if isinstance(subpix, DeviceShifts):
+                offset_dev, subpix = ptr(subpix.dev), subpix.host
+            x0, y0 = subpix
+            check(
+                _hip.lib().jd_gmm_prior_subpix_fwd_bwd(
+                    self._handle, ptr(flux), H, W, int(stride), int(sy), int(sx), c_float(x0), c_float(y0),
+                    int(bool(marginalize)), c_float(value_scale), ptr(value_out), int(accumulate_value), c_float(grad_coef),
+                    ptr(grad), ptr(argmax_out), shift_dev, offset_dev, stream_ptr(flux.device),
+                )
+            )
+            return
         if band_out is not None:
             if grad is not None or argmax_out is not None:
                 raise ValueError("band_out excludes grad and argmax_out")
@@ -605,7 +622,8 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     """Scalar GMM patch log-prior with its HIP gradient (priors/patches/core.py:227-246)."""
 
     @staticmethod
-    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None, patch_norm=None):
+    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None, patch_norm=None, subpix=None):
+        """``subpix``: the offsets (x0, y0) of a sub-pixel cycle spin (None: none)."""
         image = require_hip_tensor(flux, "flux")
         value = torch.empty(1, dtype=torch.float32, device=image.device)
         grad = None
@@ -613,7 +631,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
             grad = torch.zeros(image.shape[-2:], dtype=torch.float32, device=image.device)
         handle.prior_fwd_bwd(
             image.reshape(image.shape[-2:]), stride, shifts, value, value_scale, grad=grad, grad_coef=value_scale,
-            marginalize=marginalize, norm=norm, patch_norm=patch_norm,
+            marginalize=marginalize, norm=norm, patch_norm=patch_norm, subpix=subpix,
         )
         ctx.grad, ctx.shape = grad, flux.shape
         return value.reshape(())
@@ -621,7 +639,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_value):
         # (ctx.grad is the finished gradient with respect to the raw flux: the library applied the norm's chain rule)
-        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None, None
+        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None, None, None
 
 
 def elementwise_prior_subpix(kind, flux, alpha, beta, log_const, shifts, value_out, grad_coef, grad=None):

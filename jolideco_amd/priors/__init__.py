@@ -1,5 +1,5 @@
 from .core import ExponentialPrior, InverseGammaPrior, Prior, Priors, SmoothnessPrior, UniformPrior
-from .patches import GaussianMixtureModel, GMMPatchPrior, MultiScalePrior
+from .patches import GaussianMixtureModel, GMMPatchPrior, MultiScalePrior, SubpixelGMMPatchPrior
 
 PRIOR_REGISTRY = {
     "uniform": UniformPrior,
@@ -13,6 +13,7 @@ __all__ = [
     "GaussianMixtureModel",
     "GMMPatchPrior",
     "MultiScalePrior",
+    "SubpixelGMMPatchPrior",
     "ExponentialPrior",
     "UniformPrior",
     "InverseGammaPrior",

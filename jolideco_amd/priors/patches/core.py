@@ -6,11 +6,13 @@ import torch
 
 from ...utils.norms import IdentityImageNorm, ImageNorm, PatchNorm, SubtractMeanPatchNorm
 from ...utils.numpy import gaussian_kernel_2d
-from ...utils.torch import TORCH_DEFAULT_DEVICE, cycle_spin_shifts, cycle_spin_shifts_many, get_default_generator
+from ...utils.torch import (
+    TORCH_DEFAULT_DEVICE, cycle_spin_shifts, cycle_spin_shifts_many, get_default_generator, subpixel_offsets,
+)
 from ..core import Prior
 from .gmm import GaussianMixtureModel
 
-__all__ = ["GMMPatchPrior", "MultiScalePrior"]
+__all__ = ["GMMPatchPrior", "SubpixelGMMPatchPrior", "MultiScalePrior"]
 
 log = logging.getLogger(__name__)
 
@@ -19,9 +21,9 @@ class GMMPatchPrior(Prior):
     """Patch prior: expected (max or marginal) GMM log-likelihood of all overlapping patches.
 
     Same constructor as the reference.  8x8 and 16x16 patches (64 / 256 features) have kernels; a 16x16 prior runs the
-    whole-image dense pass only (`shardable`, `supports_fused_step`, `supports_phases` are False for it).  Options that are not on the accelerated path
-    (``cycle_spin_subpix``, ``jitter``) raise
-    NotImplementedError instead of silently running something else.
+    whole-image dense pass only (`shardable`, `supports_fused_step`, `supports_phases` are False for it).  The two switches of
+    this constructor that are not on its accelerated path (``cycle_spin_subpix``, ``jitter``) raise NotImplementedError
+    instead of silently running something else; the sub-pixel cycle spin is the subclass `SubpixelGMMPatchPrior`.
 
     ``patch_norm``: `SubtractMeanPatchNorm` or `StandardizedSubtractMeanPatchNorm` (relative contrast, (p - mean) / mean),
     by default the one the mixture was trained with (``gmm.meta.patch_norm``, the ``PNPTYPE`` keyword of a table file).
@@ -56,10 +58,11 @@ class GMMPatchPrior(Prior):
             raise ValueError("stride must be given either explicitly or through gmm.meta.stride")
         self.cycle_spin = cycle_spin
         if cycle_spin_subpix:
-            raise NotImplementedError("cycle_spin_subpix is not implemented in jolideco_amd")
+            raise NotImplementedError("cycle_spin_subpix is not an option of GMMPatchPrior in jolideco_amd: the sub-pixel "
+                                      "cycle spin is the class SubpixelGMMPatchPrior (same arguments)")
         if jitter:
             raise NotImplementedError("jitter is not implemented in jolideco_amd")
-        self.cycle_spin_subpix = False
+        self.cycle_spin_subpix = False  # (True in `SubpixelGMMPatchPrior` only)
         self.jitter = False
         # shifts are ALWAYS drawn from a host generator (torch default seed), see utils/torch.py
         self.generator = generator if generator is not None else get_default_generator("cpu")
@@ -82,9 +85,16 @@ class GMMPatchPrior(Prior):
         return self.gmm.patch_shape
 
     @property
+    def shift_kind(self):
+        """What `draw_shifts` returns: "roll" -- a pair of integer rolls or None -- or, with ``cycle_spin_subpix``,
+        "roll+subpixel": the pair (roll or None, (x0, y0))."""
+        return "roll+subpixel" if self.cycle_spin_subpix else "roll"
+
+    @property
     def _full_path(self):
-        """8x8 patches run every form of the pass; 16x16 patches (D = 256) have the whole-image dense pass only."""
-        return tuple(self.patch_shape) == (8, 8)
+        """8x8 patches run every form of the pass; 16x16 patches (D = 256) and a sub-pixel cycle spin have the whole-image
+        pass only."""
+        return tuple(self.patch_shape) == (8, 8) and not self.cycle_spin_subpix
 
     @property
     def shardable(self):
@@ -113,13 +123,18 @@ class GMMPatchPrior(Prior):
         return self.stride**2 / (self.patch_shape[0] * self.patch_shape[1])
 
     def draw_shifts(self):
-        """One pair of cycle-spin draws (None when cycle_spin is off)."""
+        """One pair of cycle-spin draws (None when cycle_spin is off); with ``cycle_spin_subpix`` the pair
+        (that, (x0, y0)): the roll is drawn first, then the offsets, x0 first -- the reference's order."""
         shifts = cycle_spin_shifts(self.patch_shape, self.generator) if self.cycle_spin else None
+        if self.cycle_spin_subpix:
+            shifts = (shifts, subpixel_offsets(self.generator))
         self.last_shifts = shifts
         return shifts
 
     def draw_shifts_many(self, n):
         """The next `n` pairs of cycle-spin draws, in order (an epoch's worth, `FitSession._plan_epoch`)."""
+        if self.cycle_spin_subpix:  # (integer and float draws alternate per evaluation: one by one)
+            return [self.draw_shifts() for _ in range(n)]
         if not self.cycle_spin:
             self.last_shifts = None
             return [None] * n
@@ -131,28 +146,40 @@ class GMMPatchPrior(Prior):
         """Differentiable log-prior of a (1, 1, H, W) HIP tensor; draws one pair of shifts."""
         from ...ops import GMMPatchPriorFunction
 
-        shifts = self.draw_shifts()
+        shifts, subpix = self._split_shifts(self.draw_shifts())
         scale = self.log_like_weight / flux.numel()
         return GMMPatchPriorFunction.apply(
-            flux, self.gmm.handle(flux.device), self.stride, shifts, self.marginalize, scale, self.norm, self.patch_norm
+            flux, self.gmm.handle(flux.device), self.stride, shifts, self.marginalize, scale, self.norm, self.patch_norm, subpix
         )
+
+    def _split_shifts(self, shifts):
+        """(roll, sub-pixel offsets or None) of a draw of `draw_shifts`."""
+        if not self.cycle_spin_subpix:
+            return shifts, None
+        if not (isinstance(shifts, tuple) and len(shifts) == 2 and shifts[1] is not None and not isinstance(shifts[1], int)):
+            raise ValueError(f"a prior with cycle_spin_subpix takes the pair (roll or None, (x0, y0)) as shifts, got {shifts!r}")
+        return shifts
 
     def device_fwd_bwd(self, flux, value_out, grad=None, coef=0.0, patch_rows=None, shifts="draw", band_out=None, phases=3):
         """Fused path: value -> device scalar, ``grad += coef * d logprior / d flux``; with ``band_out`` the gradient of
         the shard ``patch_rows`` goes, un-accumulated, to the band of the rolled frame it covers (sharded joint fit)."""
         if isinstance(shifts, str):
             shifts = self.draw_shifts()
+        shifts, subpix = self._split_shifts(shifts)
         scale = self.log_like_weight / flux.numel()
         self.gmm.handle(flux.device).prior_fwd_bwd(
             flux.reshape(flux.shape[-2:]), self.stride, shifts, value_out, scale, grad=grad, grad_coef=coef * scale,
             marginalize=self.marginalize, patch_rows=patch_rows or (0, -1), band_out=band_out, phases=phases, norm=self.norm,
-            patch_norm=self.patch_norm,
+            patch_norm=self.patch_norm, subpix=subpix,
         )
 
     def device_fwd_bwd_step(self, flux, value_out, coef, step, shifts="draw", phases=3):
         """`device_fwd_bwd` of the WHOLE prior with the component's optimizer step applied by its gather kernel:
         ``step.grad_flux`` holds every other gradient term; theta, the moments and the new flux are written in place
         (jd_gmm_prior_fwd_bwd_step).  Same numbers as `device_fwd_bwd` followed by the stand-alone step."""
+        if self.cycle_spin_subpix:
+            raise NotImplementedError("a GMMPatchPrior with cycle_spin_subpix has no fused optimizer step: call "
+                                      "device_fwd_bwd and step separately")
         if isinstance(shifts, str):
             shifts = self.draw_shifts()
         scale = self.log_like_weight / flux.numel()
@@ -172,7 +199,14 @@ class GMMPatchPrior(Prior):
         return torch.zeros_like(flux)
 
     def check_hessian_ones(self):
-        """Raise where `hessian_ones` (``compute_error=True``) is not available: any patch norm but subtract-mean."""
+        """Raise where `hessian_ones` (``compute_error=True``) is not available: any patch norm but subtract-mean, and a
+        sub-pixel cycle spin -- the zero-padded stencil of a constant image is not constant at the border and the seam of
+        the roll, so a constant vector is not in the null space of the patches' quadratic forms."""
+        if self.cycle_spin_subpix:
+            raise NotImplementedError(
+                "compute_error=True is not implemented for a GMMPatchPrior with cycle_spin_subpix: the Hessian product "
+                "with ones is not zero behind the zero-padded sub-pixel stencil"
+            )
         if not isinstance(self.patch_norm, SubtractMeanPatchNorm):
             name = self.patch_norm.to_dict().get("type", type(self.patch_norm).__name__)
             raise NotImplementedError(
@@ -186,7 +220,8 @@ class GMMPatchPrior(Prior):
     def to_dict(self):
         data = super().to_dict()
         data.update(
-            stride=int(self.stride), cycle_spin=bool(self.cycle_spin), cycle_spin_subpix=False, jitter=False,
+            stride=int(self.stride), cycle_spin=bool(self.cycle_spin), cycle_spin_subpix=bool(self.cycle_spin_subpix),
+            jitter=False,
             gmm=self.gmm.to_dict(), norm=self.norm.to_dict(), patch_norm=self.patch_norm.to_dict(),
             device=str(self.device),
         )
@@ -204,7 +239,33 @@ class GMMPatchPrior(Prior):
         kwargs["norm"] = ImageNorm.from_dict(kwargs.pop("norm", {"type": "identity"}))
         if "patch_norm" in kwargs:
             kwargs["patch_norm"] = PatchNorm.from_dict(kwargs["patch_norm"])
+        if kwargs.get("cycle_spin_subpix") and cls is GMMPatchPrior:  # (a header with PSUBSPIN = T: the subclass)
+            cls = SubpixelGMMPatchPrior
         return cls(**kwargs)
+
+
+class SubpixelGMMPatchPrior(GMMPatchPrior):
+    """`GMMPatchPrior` with the reference's ``cycle_spin_subpix=True``: behind the roll the normed image is shifted by a
+    random sub-pixel offset (x0, y0) in [-0.5, 0.5]^2 -- the 3 x 3 stencil of bilinear weights of
+    jolideco/utils/torch.py:122-143, zero outside the rolled image -- drawn per evaluation from ``generator`` after the two
+    roll draws, x0 first.  A class of its own because `GMMPatchPrior(cycle_spin_subpix=True)` keeps raising; the arguments
+    are `GMMPatchPrior`'s (``cycle_spin_subpix``, if given, must be true), `to_dict` writes ``cycle_spin_subpix: True``
+    under the type "gmm-patches" -- what the reference writes and reads -- and `GMMPatchPrior.from_dict`, YAML and the
+    FITS keyword ``PSUBSPIN`` give this class back.
+
+    Two streaming kernels around the unchanged pass (csrc/gmm_subpix.hip); every norm, patch norm, both patch sizes and both
+    modes work with it.  The prior is evaluated whole (`shardable`, `supports_fused_step`, `supports_phases` are False;
+    `device_fwd_bwd_step` raises), its `draw_shifts` returns the pair ``(roll or None, (x0, y0))``
+    (``shift_kind = "roll+subpixel"``), a session with it runs by-value epochs only, it has no ``compute_error``
+    (`check_hessian_ones`) and cannot be the inner prior of a `MultiScalePrior`."""
+
+    def __init__(self, gmm=None, stride=None, cycle_spin=True, cycle_spin_subpix=True, generator=None, norm=None,
+                 patch_norm=None, jitter=False, marginalize=False, device=TORCH_DEFAULT_DEVICE):
+        if not cycle_spin_subpix:
+            raise ValueError("SubpixelGMMPatchPrior is the prior with cycle_spin_subpix=True: use GMMPatchPrior without it")
+        super().__init__(gmm=gmm, stride=stride, cycle_spin=cycle_spin, generator=generator, norm=norm, patch_norm=patch_norm,
+                         jitter=jitter, marginalize=marginalize, device=device)
+        self.cycle_spin_subpix = True
 
 
 MULTISCALE_MAX_LEVELS = 5  # pooling factors 1 ... 16; the widest blur has 43 taps (JD_MULTISCALE_MAX_LEVELS)
@@ -234,7 +295,8 @@ class MultiScalePrior(Prior):
     Same constructor as the reference.  ``weights`` (default 1 / n_levels each) are stored as log-weights and normalised by
     a softmax, in float32, as the reference does; they are constants of the prior here (the reference trains
     ``_log_weights``), like the parameters of the image norms.  At most 5 levels.  ``prior``: any prior of this package with a
-    `device_fwd_bwd` except another `MultiScalePrior`.
+    `device_fwd_bwd` except another `MultiScalePrior` and a `SubpixelGMMPatchPrior` (NotImplementedError:
+    its draw is a roll and two offsets, not a level's roll).
 
     ``cycle_spin=True`` (the default): the full-resolution flux is rolled by one draw of
     ``cycle_spin_shifts(prior.patch_shape, prior.generator)`` in front of the levels -- what the reference's
@@ -258,6 +320,9 @@ class MultiScalePrior(Prior):
         super().__init__()
         if isinstance(prior, MultiScalePrior) or not isinstance(prior, Prior) or type(prior).device_fwd_bwd is Prior.device_fwd_bwd:
             raise ValueError("the inner prior must be a prior of jolideco_amd with a device_fwd_bwd, and not a MultiScalePrior")
+        if getattr(prior, "shift_kind", None) == "roll+subpixel":
+            raise NotImplementedError(f"a MultiScalePrior around a {type(prior).__name__} with cycle_spin_subpix is not "
+                                      "implemented in jolideco_amd: its draw (roll, offsets) is not a level's roll")
         n_levels = int(n_levels)
         if not 1 <= n_levels <= MULTISCALE_MAX_LEVELS:
             raise ValueError(f"n_levels must be in [1, {MULTISCALE_MAX_LEVELS}], got {n_levels}")
