@@ -487,6 +487,36 @@ int jd_gmm_prior_subpix_fwd_bwd(jd_gmm* gmm, const float* flux, int H, int W, in
                                 int accumulate_value, float grad_coef, float* grad_flux_accum, int32_t* argmax_out,
                                 const int* shift_dev, const float* offset_dev, void* stream);
 
+/* The same prior with `jitter=True` (priors/patches/core.py:189-220; utils/torch.py:278-334): behind the norm and the roll
+ * every patch row and every patch column is moved by a draw of its own.  With P the patch size of the handle (8 or 16),
+ * `stride` the prior's stride in [1, P] and overlap = P - stride, along an axis of length n
+ *   count = len(arange(overlap, n - stride - overlap, stride)),   pos_i = overlap + i stride + draw_i,
+ * n_y = count(H), n_x = count(W), and patch (i, j) is rolled_normed[py_i : py_i + P, px_j : px_j + P].  jitter_y_dev /
+ * jitter_x_dev: DEVICE arrays of n_y / n_x int32, the draws themselves (the reference draws x first), each in
+ * [-overlap, overlap].  They live on the device and cannot be validated here: inside the kernels a draw is CLAMPED to that
+ * range (the Python layer validates what it uploads), and the flux is read through a non-negative mod, so no value of a
+ * draw reads outside the image.  An axis is safe when overlap + (count - 1) stride + overlap <= n - P: no draw can push a
+ * patch outside (the reference has no such check and fails at random).
+ * Two streaming kernels around the unchanged pass: the first writes the patches side by side,
+ *   S[i P + a, j P + b] = n(flux[(py_i + a - shift_y) mod H, (px_j + b - shift_x) mod W]),
+ * and zeroes an image G of the same shape; jd_gmm_prior_fwd_bwd runs on S ((n_y P, n_x P), stride P, no roll, identity
+ * norm, the handle's patch norm), G = grad_coef d(sum v_patch)/dS; the second adds, per flux pixel with
+ * (Y, X) = ((y + shift_y) mod H, (x + shift_x) mod W),
+ *   n'(flux[y, x]) sum_{i: 0 <= Y - py_i < P} sum_{j: 0 <= X - px_j < P} G[i P + (Y - py_i), j P + (X - px_j)]
+ * to grad_flux_accum, i ascending then j ascending, no atomics: run-to-run identical.  A pixel whose sum is exactly 0
+ * (no patch covers it, or under a norm n' may be infinite) is not written.  S and G (about 4 x the image each at stride
+ * P / 2) belong to the handle and grow on demand: after the first call for a shape nothing is allocated.
+ * Value, value_scale, accumulate_value, grad_coef, marginalize, the image norm and the patch norm of the handle (left as
+ * found) mean what they mean for jd_gmm_prior_fwd_bwd; argmax_out: one int32 per patch in order i n_x + j; shift_dev as
+ * there.  With stride == P the result is that call's on the crop flux[:n_y P, :n_x P], bit for bit.  The WHOLE prior only
+ * (no patch row shard, no band, no phases, no fused optimizer step); D = 64 and D = 256 handles.
+ * JD_ERR_INVALID, nothing launched, the handle usable: a NULL gmm, flux, value_out or jitter array; n_y == 0 or n_x == 0;
+ * an axis that is not safe; stride outside [1, P]; a staged image of 2^31 elements or more. */
+int jd_gmm_prior_jitter_fwd_bwd(jd_gmm* gmm, const float* flux, int H, int W, int stride, int shift_y, int shift_x,
+                                const int* jitter_y_dev, const int* jitter_x_dev, int marginalize, float value_scale,
+                                float* value_out, int accumulate_value, float grad_coef, float* grad_flux_accum,
+                                int32_t* argmax_out, const int* shift_dev, void* stream);
+
 /* Diagnostics of the screened arg-max path, read without synchronisation from host-mapped memory the last block of a
  * pass writes: out[0..4] = {generation of the last finished pass, it fell back to the dense fp32 kernel (0 / 1), bucket
  * slots its surviving records used, patches it covered, gradient rows per patch the record buffer has room for now}.

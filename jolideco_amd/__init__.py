@@ -19,6 +19,7 @@ from .priors import (
     GaussianMixtureModel,
     GMMPatchPrior,
     InverseGammaPrior,
+    JitteredGMMPatchPrior,
     MultiScalePrior,
     Priors,
     SmoothnessPrior,
@@ -45,6 +46,7 @@ __all__ = [
     "GMMPatchPrior",
     "MultiScalePrior",
     "SubpixelGMMPatchPrior",
+    "JitteredGMMPatchPrior",
     "UniformPrior",
     "InverseGammaPrior",
     "ExponentialPrior",

@@ -663,6 +663,16 @@ class FitSession:
         # four-word slot per evaluation -- by-value epochs only)
         self.has_subpix_patches = any(getattr(getattr(c, "prior", None), "shift_kind", None) == "roll+subpixel"
                                       for c in components.values())
+        # (a draw of a patch prior with a jittered grid is a roll and one offset per patch row and patch column of the
+        # component's shape: by-value epochs only.  The shape is known here: an unsafe one is refused now, not some epochs in)
+        self.has_jitter_patches = False
+        for name, c in components.items():
+            if getattr(getattr(c, "prior", None), "shift_kind", None) == "roll+jitter":
+                self.has_jitter_patches = True
+                try:
+                    c.prior.check_shape(tuple(c.shape))
+                except ValueError as exc:
+                    raise ValueError(f"flux component {name!r}: {exc}") from None
         if multiscale and deconvolver.checkpoint_path is not None:
             prior = components[multiscale[0]].prior
             raise NotImplementedError(
@@ -983,9 +993,13 @@ class FitSession:
 
     def _open_policy(self):
         """`graph_policy` of the "auto" mode before anything is measured: "undecided" -- or, for a session that can only run
-        by-value epochs because of a patch prior with a sub-pixel cycle spin, that fact (nothing will be measured)."""
+        by-value epochs because of a patch prior with a sub-pixel cycle spin or a jittered grid, that fact (nothing will be
+        measured)."""
         if getattr(self, "has_subpix_patches", False):
             return "by value (a SubpixelGMMPatchPrior draws a roll and two offsets per evaluation: no planned epochs)"
+        if getattr(self, "has_jitter_patches", False):
+            return ("by value (a JitteredGMMPatchPrior draws a roll and one offset per patch row and patch column per "
+                    "evaluation: no planned epochs)")
         return "undecided"
 
     def _planned_capable(self):
@@ -993,11 +1007,13 @@ class FitSession:
         by-value path), no event brackets around collectives, no kernel timers, no sparse component (its stepper takes
         its bias terms by value: by-value epochs only, nothing is captured) and no multi-scale prior (a draw is one pair
         per level on grids of different sizes: a captured epoch would bake them in) and no patch prior with a sub-pixel
-        cycle spin (its draw is a roll and two offsets; the two-word slots hold one or the other).  The options of torch.optim keep
+        cycle spin (its draw is a roll and two offsets; the two-word slots hold one or the other) or a jittered grid (its
+        draw is a roll and an array per axis).  The options of torch.optim keep
         planned and captured epochs -- `jd_optimizer_step` reads the bias terms from device memory like the fused steps --
         except a momentum (SGD): the first step of a parameter makes the buffer the gradient, later ones read it, and a
         replayed launch cannot know which it is; a session with ``momentum != 0`` runs by-value epochs only."""
-        if self.has_sparse or getattr(self, "has_multiscale", False) or getattr(self, "has_subpix_patches", False):
+        if (self.has_sparse or getattr(self, "has_multiscale", False) or getattr(self, "has_subpix_patches", False)
+                or getattr(self, "has_jitter_patches", False)):
             return False
         cfg = self.cfg
         if optimizer_options(cfg)[0].get("momentum"):
@@ -1099,7 +1115,14 @@ class FitSession:
         generators advance as in `_plan_epoch`, and while the step runs `last_shifts` of a prior is the step's draw (a
         replaced `_optimizer_step` may read it).  Passed in, so that a prior run in two phases does not draw twice.  (Not
         for a sharded joint step: there a rank draws for the priors it evaluates, in its order -- `_sharded_priors`.)"""
-        return {ci: self.priors[ci].draw_shifts() for ci in self._plan_slots()[0]}
+        return {ci: self._draw_prior(ci) for ci in self._plan_slots()[0]}
+
+    def _draw_prior(self, ci):
+        """One draw of prior `ci`; a jittered patch grid draws for the shape of its component's flux"""
+        prior = self.priors[ci]
+        if getattr(prior, "shift_kind", None) == "roll+jitter":
+            return prior.draw_shifts(tuple(self.states[ci].shape))
+        return prior.draw_shifts()
 
     # ---- the second frame's adjoints beside the first's -----------------------------------------------------------------
     def _likelihood_addends(self, early):

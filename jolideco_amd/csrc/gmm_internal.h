@@ -693,8 +693,8 @@ struct jd_gmm {
   jd::GmmPass pass;
   jd::ImageNormArgs norm{};  // image norm the next prior call takes (jd_gmm_set_image_norm; kind 0 = identity)
   int patch_norm = jd::PATCH_NORM_SUBTRACT_MEAN;  // patch norm the next prior call takes (jd_gmm_set_patch_norm)
-  jd::DevBuf<float> normed;  // n(flux) of the pass, (H, W): what phase 1 reads in place of the flux (sub-pixel cycle spin: S)
-  jd::DevBuf<float> subpix_grad;  // sub-pixel cycle spin (gmm_subpix.hip): G, the gradient with respect to S, (H, W)
+  jd::DevBuf<float> normed;  // n(flux) of the pass, (H, W): what phase 1 reads in place of the flux (sub-pixel cycle spin, jitter: S)
+  jd::DevBuf<float> subpix_grad;  // sub-pixel cycle spin (gmm_subpix.hip), jitter (gmm_jitter.hip): G, the gradient with respect to S, the shape of S
   int K = 0;
   bool triangular = true;  // every P_k upper triangular -> zero blocks are skipped
   int n_cu = 256;

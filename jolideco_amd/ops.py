@@ -407,6 +407,52 @@ class DeviceShifts:
         self.dev, self.host = dev, host
 
 
+class JitterRing:
+    """The draws of a jittered patch grid on their way to the device without a host synchronisation: a ring of pinned host
+    rows and device rows (as `StepScalars` does for the step scalars).  `upload` fills the next row, enqueues a non-blocking
+    copy on the current stream and returns the two device views; the caller records the row's event behind the launch that
+    reads them (`done`), and a row is reused only after that event -- RING evaluations later, so the wait is idle."""
+
+    RING = 8
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.host, self.dev, self.events = [None] * self.RING, [None] * self.RING, [None] * self.RING
+        self.used = [False] * self.RING
+        self.slot = 0
+
+    def upload(self, jitter_y, jitter_x):
+        """(device int32 [n_y], device int32 [n_x], slot) of two host int tensors"""
+        n_y, n_x = int(jitter_y.numel()), int(jitter_x.numel())
+        slot, n = self.slot, n_y + n_x
+        if self.used[slot]:
+            self.events[slot].synchronize()
+            self.used[slot] = False
+        if self.host[slot] is None or self.host[slot].numel() < n:
+            size = max(256, 2 * n)
+            self.host[slot] = torch.empty(size, dtype=torch.int32).pin_memory()
+            self.dev[slot] = torch.empty(size, dtype=torch.int32, device=self.device)
+            self.events[slot] = torch.cuda.Event()
+        host, dev = self.host[slot], self.dev[slot]
+        host[:n_y].copy_(jitter_y)
+        host[n_y:n].copy_(jitter_x)
+        dev[:n].copy_(host[:n], non_blocking=True)
+        self.slot = (slot + 1) % self.RING
+        return dev[:n_y], dev[n_y:n], slot
+
+    def done(self, slot):
+        self.events[slot].record()
+        self.used[slot] = True
+
+
+def jitter_counts(shape, patch, stride):
+    """(n_y, n_x) of the jittered patch grid (`utils.torch.jitter_grid`; raises ValueError for an unsafe shape)"""
+    from .utils.torch import jitter_grid
+
+    base_y, base_x = jitter_grid(shape, (patch, patch), stride)
+    return int(base_y.numel()), int(base_x.numel())
+
+
 class GmmHandle:
     """GMM constants in MFMA fragment order on the device (jd_gmm)."""
 
@@ -435,6 +481,7 @@ class GmmHandle:
         with torch.cuda.device(self.device):
             check(_hip.lib().jd_gmm_create(K, D, as_fp(pc), as_fp(mp), as_fp(const_k), as_fp(pw), ctypes.byref(handle)))
         self._handle = handle
+        self._jitter_ring = None  # (`JitterRing`, made by the first jittered evaluation)
         if const_float64 is not None:
             residual = np.ascontiguousarray(np.asarray(const_float64, dtype=np.float64) - const_k.astype(np.float64), dtype=np.float32)
             if residual.shape != (K,):
@@ -474,13 +521,18 @@ class GmmHandle:
 
     def prior_fwd_bwd(self, flux, stride, shifts, value_out, value_scale, grad=None, grad_coef=0.0,
                       marginalize=False, patch_rows=(0, -1), accumulate_value=False, argmax_out=None, band_out=None, phases=3,
-                      norm=None, patch_norm=None, subpix=None):
+                      norm=None, patch_norm=None, subpix=None, jitter=None):
         """``band_out``: instead of accumulating into ``grad``, write the gradient of the patch rows ``patch_rows`` as the
         band of the rolled frame they cover (jd_gmm_prior_band_fwd_bwd; `band_rows` gives its extent).
         ``norm``: the prior's image norm (None = identity); the gradient is the one with respect to the raw flux.
         ``patch_norm``: the prior's patch norm (None = subtract-mean).
         ``subpix``: the offsets (x0, y0) of a sub-pixel cycle spin -- or a `DeviceShifts` whose ``dev`` holds them as two
-        float32 in device memory -- applied behind the roll (jd_gmm_prior_subpix_fwd_bwd): the whole prior only."""
+        float32 in device memory -- applied behind the roll (jd_gmm_prior_subpix_fwd_bwd): the whole prior only.
+        ``jitter``: the draws (jitter_y, jitter_x) of a jittered patch grid (jd_gmm_prior_jitter_fwd_bwd), one per patch row
+        and one per patch column of `utils.torch.jitter_grid`, each in [-overlap, overlap]: host sequences or tensors --
+        validated here, sent through a pinned ring without a host synchronisation -- or int32 tensors on the flux's device,
+        which the kernels read as they are (nothing can be validated without a synchronisation: they clamp).  The whole prior
+        only; excludes ``subpix``.  An unsafe shape raises ValueError."""
         flux = require_hip_tensor(flux, "flux")
         self.set_image_norm(norm)
         self.set_patch_norm(patch_norm)
@@ -493,6 +545,44 @@ class GmmHandle:
                 raise ValueError("device-resident shifts are not available for the band form")
             shift_dev, shifts = ptr(shifts.dev), shifts.host
         sy, sx = (0, 0) if shifts is None else shifts
+        if jitter is not None:
+            if subpix is not None or band_out is not None or phases != 3 or tuple(patch_rows) != (0, -1):
+                raise ValueError("a jittered patch grid evaluates the whole prior: no subpix, patch_rows, band_out or phases")
+            patch = 8 if self.D == 64 else 16
+            n_y, n_x = jitter_counts((H, W), patch, stride)
+            overlap = patch - int(stride)
+            jitter_y, jitter_x = jitter
+            on_device = [isinstance(j, torch.Tensor) and j.device.type == "cuda" for j in (jitter_y, jitter_x)]
+            slot = None
+            if all(on_device):
+                for name, j, n in (("jitter_y", jitter_y, n_y), ("jitter_x", jitter_x, n_x)):
+                    if j.dtype != torch.int32 or not j.is_contiguous() or j.numel() != n or j.device != flux.device:
+                        raise ValueError(f"{name} on the device must be a contiguous int32 tensor of {n} draws on {flux.device}")
+            elif any(on_device):
+                raise ValueError("jitter_y and jitter_x must both be on the host or both on the device")
+            else:
+                jitter_y, jitter_x = (torch.as_tensor(j).reshape(-1) for j in (jitter_y, jitter_x))
+                for name, j, n in (("jitter_y", jitter_y, n_y), ("jitter_x", jitter_x, n_x)):
+                    if j.dtype not in (torch.int32, torch.int64) or j.numel() != n:
+                        raise ValueError(f"{name} must hold {n} integer draws for a ({H}, {W}) image at stride {stride}, got "
+                                         f"{j.numel()} of {j.dtype}")
+                    if n and (int(j.min()) < -overlap or int(j.max()) > overlap):
+                        raise ValueError(f"{name} has a draw outside [-{overlap}, {overlap}]")
+                if self._jitter_ring is None:
+                    self._jitter_ring = JitterRing(flux.device)
+                with torch.cuda.device(flux.device):
+                    jitter_y, jitter_x, slot = self._jitter_ring.upload(jitter_y, jitter_x)
+            check(
+                _hip.lib().jd_gmm_prior_jitter_fwd_bwd(
+                    self._handle, ptr(flux), H, W, int(stride), int(sy), int(sx), ptr(jitter_y), ptr(jitter_x),
+                    int(bool(marginalize)), c_float(value_scale), ptr(value_out), int(accumulate_value), c_float(grad_coef),
+                    ptr(grad), ptr(argmax_out), shift_dev, stream_ptr(flux.device),
+                )
+            )
+            if slot is not None:
+                with torch.cuda.device(flux.device):
+                    self._jitter_ring.done(slot)
+            return
         if subpix is not None:
             if band_out is not None or phases != 3 or tuple(patch_rows) != (0, -1):
                 raise ValueError("a sub-pixel cycle spin evaluates the whole prior: no patch_rows, band_out or phases")
@@ -622,8 +712,10 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     """Scalar GMM patch log-prior with its HIP gradient (priors/patches/core.py:227-246)."""
 
     @staticmethod
-    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None, patch_norm=None, subpix=None):
-        """``subpix``: the offsets (x0, y0) of a sub-pixel cycle spin (None: none)."""
+    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None, patch_norm=None, subpix=None,
+                jitter=None):
+        """``subpix``: the offsets (x0, y0) of a sub-pixel cycle spin (None: none); ``jitter``: the draws (jitter_y, jitter_x)
+        of a jittered patch grid (None: none)."""
         image = require_hip_tensor(flux, "flux")
         value = torch.empty(1, dtype=torch.float32, device=image.device)
         grad = None
@@ -631,7 +723,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
             grad = torch.zeros(image.shape[-2:], dtype=torch.float32, device=image.device)
         handle.prior_fwd_bwd(
             image.reshape(image.shape[-2:]), stride, shifts, value, value_scale, grad=grad, grad_coef=value_scale,
-            marginalize=marginalize, norm=norm, patch_norm=patch_norm, subpix=subpix,
+            marginalize=marginalize, norm=norm, patch_norm=patch_norm, subpix=subpix, jitter=jitter,
         )
         ctx.grad, ctx.shape = grad, flux.shape
         return value.reshape(())
@@ -639,7 +731,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_value):
         # (ctx.grad is the finished gradient with respect to the raw flux: the library applied the norm's chain rule)
-        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None, None, None
+        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None, None, None, None
 
 
 def elementwise_prior_subpix(kind, flux, alpha, beta, log_const, shifts, value_out, grad_coef, grad=None):

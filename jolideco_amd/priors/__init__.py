@@ -1,5 +1,5 @@
 from .core import ExponentialPrior, InverseGammaPrior, Prior, Priors, SmoothnessPrior, UniformPrior
-from .patches import GaussianMixtureModel, GMMPatchPrior, MultiScalePrior, SubpixelGMMPatchPrior
+from .patches import GaussianMixtureModel, GMMPatchPrior, JitteredGMMPatchPrior, MultiScalePrior, SubpixelGMMPatchPrior
 
 PRIOR_REGISTRY = {
     "uniform": UniformPrior,
@@ -14,6 +14,7 @@ __all__ = [
     "GMMPatchPrior",
     "MultiScalePrior",
     "SubpixelGMMPatchPrior",
+    "JitteredGMMPatchPrior",
     "ExponentialPrior",
     "UniformPrior",
     "InverseGammaPrior",

@@ -7,12 +7,13 @@ import torch
 from ...utils.norms import IdentityImageNorm, ImageNorm, PatchNorm, SubtractMeanPatchNorm
 from ...utils.numpy import gaussian_kernel_2d
 from ...utils.torch import (
-    TORCH_DEFAULT_DEVICE, cycle_spin_shifts, cycle_spin_shifts_many, get_default_generator, subpixel_offsets,
+    TORCH_DEFAULT_DEVICE, cycle_spin_shifts, cycle_spin_shifts_many, get_default_generator, jitter_draws, jitter_grid,
+    jitter_stride_check, subpixel_offsets,
 )
 from ..core import Prior
 from .gmm import GaussianMixtureModel
 
-__all__ = ["GMMPatchPrior", "SubpixelGMMPatchPrior", "MultiScalePrior"]
+__all__ = ["GMMPatchPrior", "SubpixelGMMPatchPrior", "JitteredGMMPatchPrior", "MultiScalePrior"]
 
 log = logging.getLogger(__name__)
 
@@ -23,7 +24,8 @@ class GMMPatchPrior(Prior):
     Same constructor as the reference.  8x8 and 16x16 patches (64 / 256 features) have kernels; a 16x16 prior runs the
     whole-image dense pass only (`shardable`, `supports_fused_step`, `supports_phases` are False for it).  The two switches of
     this constructor that are not on its accelerated path (``cycle_spin_subpix``, ``jitter``) raise NotImplementedError
-    instead of silently running something else; the sub-pixel cycle spin is the subclass `SubpixelGMMPatchPrior`.
+    instead of silently running something else; the sub-pixel cycle spin is the subclass `SubpixelGMMPatchPrior`, the
+    jittered patch grid the subclass `JitteredGMMPatchPrior`.
 
     ``patch_norm``: `SubtractMeanPatchNorm` or `StandardizedSubtractMeanPatchNorm` (relative contrast, (p - mean) / mean),
     by default the one the mixture was trained with (``gmm.meta.patch_norm``, the ``PNPTYPE`` keyword of a table file).
@@ -61,9 +63,10 @@ class GMMPatchPrior(Prior):
             raise NotImplementedError("cycle_spin_subpix is not an option of GMMPatchPrior in jolideco_amd: the sub-pixel "
                                       "cycle spin is the class SubpixelGMMPatchPrior (same arguments)")
         if jitter:
-            raise NotImplementedError("jitter is not implemented in jolideco_amd")
+            raise NotImplementedError(f"jitter is not an option of {type(self).__name__} in jolideco_amd: the jittered patch "
+                                      "grid is the class JitteredGMMPatchPrior (same arguments)")
         self.cycle_spin_subpix = False  # (True in `SubpixelGMMPatchPrior` only)
-        self.jitter = False
+        self.jitter = False  # (True in `JitteredGMMPatchPrior` only)
         # shifts are ALWAYS drawn from a host generator (torch default seed), see utils/torch.py
         self.generator = generator if generator is not None else get_default_generator("cpu")
         if self.generator.device.type != "cpu":
@@ -87,14 +90,16 @@ class GMMPatchPrior(Prior):
     @property
     def shift_kind(self):
         """What `draw_shifts` returns: "roll" -- a pair of integer rolls or None -- or, with ``cycle_spin_subpix``,
-        "roll+subpixel": the pair (roll or None, (x0, y0))."""
+        "roll+subpixel": the pair (roll or None, (x0, y0)), with ``jitter`` "roll+jitter": (roll or None, (jitter_x, jitter_y))."""
+        if self.jitter:
+            return "roll+jitter"
         return "roll+subpixel" if self.cycle_spin_subpix else "roll"
 
     @property
     def _full_path(self):
-        """8x8 patches run every form of the pass; 16x16 patches (D = 256) and a sub-pixel cycle spin have the whole-image
-        pass only."""
-        return tuple(self.patch_shape) == (8, 8) and not self.cycle_spin_subpix
+        """8x8 patches run every form of the pass; 16x16 patches (D = 256), a sub-pixel cycle spin and a jittered patch grid
+        have the whole-image pass only."""
+        return tuple(self.patch_shape) == (8, 8) and not self.cycle_spin_subpix and not self.jitter
 
     @property
     def shardable(self):
@@ -221,7 +226,7 @@ class GMMPatchPrior(Prior):
         data = super().to_dict()
         data.update(
             stride=int(self.stride), cycle_spin=bool(self.cycle_spin), cycle_spin_subpix=bool(self.cycle_spin_subpix),
-            jitter=False,
+            jitter=bool(self.jitter),
             gmm=self.gmm.to_dict(), norm=self.norm.to_dict(), patch_norm=self.patch_norm.to_dict(),
             device=str(self.device),
         )
@@ -241,6 +246,8 @@ class GMMPatchPrior(Prior):
             kwargs["patch_norm"] = PatchNorm.from_dict(kwargs["patch_norm"])
         if kwargs.get("cycle_spin_subpix") and cls is GMMPatchPrior:  # (a header with PSUBSPIN = T: the subclass)
             cls = SubpixelGMMPatchPrior
+        if kwargs.get("jitter") and cls is GMMPatchPrior:  # (a header with PJITTER = T: the subclass)
+            cls = JitteredGMMPatchPrior
         return cls(**kwargs)
 
 
@@ -266,6 +273,102 @@ class SubpixelGMMPatchPrior(GMMPatchPrior):
         super().__init__(gmm=gmm, stride=stride, cycle_spin=cycle_spin, generator=generator, norm=norm, patch_norm=patch_norm,
                          jitter=jitter, marginalize=marginalize, device=device)
         self.cycle_spin_subpix = True
+
+
+class JitteredGMMPatchPrior(GMMPatchPrior):
+    """`GMMPatchPrior` with the reference's ``jitter=True`` (jolideco/utils/torch.py:278-334): behind the norm and the roll
+    every patch row and every patch column is moved by a draw of its own in [-overlap, overlap], fresh on every evaluation
+    -- the reference's remedy against the block pattern of a fixed patch grid.  The grid is
+    ``arange(overlap, n - stride - overlap, stride)`` per axis (`utils.torch.jitter_grid`); the draws come from
+    ``generator`` after the two roll draws, the columns' first (`utils.torch.jitter_draws`), also when ``overlap == 0``.
+    A class of its own because `GMMPatchPrior(jitter=True)` keeps raising; the arguments are `GMMPatchPrior`'s (``jitter``,
+    if given, must be true; ``cycle_spin_subpix=True`` with it raises NotImplementedError), `to_dict` writes
+    ``jitter: True`` under the type "gmm-patches" -- what the reference writes and reads -- and `GMMPatchPrior.from_dict`,
+    YAML and the FITS keyword ``PJITTER`` give this class back.
+
+    The reference keeps no patch inside the image and fails with an IndexError on an unlucky draw.  Here an image shape that
+    a draw could push a patch out of is refused with a ValueError, on every evaluation path, before anything is drawn.
+    Below half a patch no shape is safe, so the constructor refuses such a stride (ValueError): the stride is in [P/2, P].
+
+    Two streaming kernels around the unchanged pass (csrc/gmm_jitter.hip); every norm, patch norm, both patch sizes and both
+    modes work with it.  The prior is evaluated whole (`shardable`, `supports_fused_step`, `supports_phases` are False;
+    `device_fwd_bwd_step` raises), its `draw_shifts(shape)` returns ``(roll or None, (jitter_x, jitter_y))``
+    (``shift_kind = "roll+jitter"``), a session with it runs by-value epochs only, and it cannot be the inner prior of a
+    `MultiScalePrior`.  ``compute_error`` works as for the plain prior: a jittered patch still has its mean subtracted."""
+
+    def __init__(self, gmm=None, stride=None, cycle_spin=True, cycle_spin_subpix=False, generator=None, norm=None,
+                 patch_norm=None, jitter=True, marginalize=False, device=TORCH_DEFAULT_DEVICE):
+        if not jitter:
+            raise ValueError("JitteredGMMPatchPrior is the prior with jitter=True: use GMMPatchPrior without it")
+        if cycle_spin_subpix:
+            raise NotImplementedError("a jittered patch grid together with cycle_spin_subpix is not implemented in jolideco_amd")
+        super().__init__(gmm=gmm, stride=stride, cycle_spin=cycle_spin, generator=generator, norm=norm, patch_norm=patch_norm,
+                         marginalize=marginalize, device=device)
+        # (a stride outside [P / 2, P] -- given, or the mixture's ``meta.stride`` -- is refused here: no shape is safe at it)
+        jitter_stride_check(max(self.patch_shape), self.stride)
+        self.jitter = True
+
+    def check_shape(self, shape):
+        """(n_y, n_x) of the grid of an image of ``shape``; ValueError for a shape that is too small or not safe"""
+        base_y, base_x = jitter_grid(shape, self.patch_shape, self.stride)
+        return int(base_y.numel()), int(base_x.numel())
+
+    def draw_shifts(self, shape=None):
+        """One draw for an image of ``shape``: ``(roll or None, (jitter_x, jitter_y))`` -- the two roll draws, then the
+        columns' draws, then the rows', the reference's order; the jitter arrays are int64 host tensors."""
+        if shape is None:
+            raise ValueError("the draw of a JitteredGMMPatchPrior depends on the image: draw_shifts(shape)")
+        n_y, n_x = self.check_shape(shape)  # (an unsafe shape raises before the generator advances)
+        roll = cycle_spin_shifts(self.patch_shape, self.generator) if self.cycle_spin else None
+        self.last_shifts = (roll, jitter_draws(self.generator, n_x, n_y, self.overlap))
+        return self.last_shifts
+
+    def draw_shifts_many(self, n, shape=None):
+        return [self.draw_shifts(shape) for _ in range(n)]
+
+    @staticmethod
+    def _split(shifts):
+        """(roll, (jitter_y, jitter_x)) -- the library's order -- of a draw of `draw_shifts`"""
+        if not (isinstance(shifts, tuple) and len(shifts) == 2 and isinstance(shifts[1], (tuple, list)) and len(shifts[1]) == 2
+                and not isinstance(shifts[1][0], (int, float))):
+            raise ValueError(f"a JitteredGMMPatchPrior takes the pair (roll or None, (jitter_x, jitter_y)) as shifts, got {shifts!r}")
+        roll, (jitter_x, jitter_y) = shifts
+        return roll, (jitter_y, jitter_x)
+
+    def __call__(self, flux, mask=None):
+        """Differentiable log-prior of a (1, 1, H, W) HIP tensor; draws once for the flux's shape."""
+        from ...ops import GMMPatchPriorFunction
+
+        roll, jitter = self._split(self.draw_shifts(flux.shape))
+        scale = self.log_like_weight / flux.numel()
+        return GMMPatchPriorFunction.apply(
+            flux, self.gmm.handle(flux.device), self.stride, roll, self.marginalize, scale, self.norm, self.patch_norm, None, jitter
+        )
+
+    def device_fwd_bwd(self, flux, value_out, grad=None, coef=0.0, patch_rows=None, shifts="draw", band_out=None, phases=3):
+        """Fused path: value -> device scalar, ``grad += coef * d logprior / d flux``.  The whole prior only; ``shifts``: a
+        draw of `draw_shifts` ("draw": one for the flux's shape)."""
+        if isinstance(shifts, str):
+            shifts = self.draw_shifts(flux.shape)
+        roll, jitter = self._split(shifts)
+        scale = self.log_like_weight / flux.numel()
+        self.gmm.handle(flux.device).prior_fwd_bwd(
+            flux.reshape(flux.shape[-2:]), self.stride, roll, value_out, scale, grad=grad, grad_coef=coef * scale,
+            marginalize=self.marginalize, patch_rows=patch_rows or (0, -1), band_out=band_out, phases=phases, norm=self.norm,
+            patch_norm=self.patch_norm, jitter=jitter,
+        )
+
+    def device_fwd_bwd_step(self, flux, value_out, coef, step, shifts="draw", phases=3):
+        raise NotImplementedError("a JitteredGMMPatchPrior has no fused optimizer step: call device_fwd_bwd and step separately")
+
+    def hessian_ones(self, flux):
+        """Zero, as for the plain prior (a jittered patch still has its mean subtracted); draws once with the flux's shape."""
+        self.check_hessian_ones()
+        self.draw_shifts(flux.shape)
+        return torch.zeros_like(flux)
+
+    def n_patch_rows(self, shape):
+        return self.check_shape(shape)[0]
 
 
 MULTISCALE_MAX_LEVELS = 5  # pooling factors 1 ... 16; the widest blur has 43 taps (JD_MULTISCALE_MAX_LEVELS)
@@ -295,8 +398,9 @@ class MultiScalePrior(Prior):
     Same constructor as the reference.  ``weights`` (default 1 / n_levels each) are stored as log-weights and normalised by
     a softmax, in float32, as the reference does; they are constants of the prior here (the reference trains
     ``_log_weights``), like the parameters of the image norms.  At most 5 levels.  ``prior``: any prior of this package with a
-    `device_fwd_bwd` except another `MultiScalePrior` and a `SubpixelGMMPatchPrior` (NotImplementedError:
-    its draw is a roll and two offsets, not a level's roll).
+    `device_fwd_bwd` except another `MultiScalePrior`, a `SubpixelGMMPatchPrior` (NotImplementedError:
+    its draw is a roll and two offsets, not a level's roll) and a `JitteredGMMPatchPrior` (NotImplementedError: its draw
+    depends on each level's shape).
 
     ``cycle_spin=True`` (the default): the full-resolution flux is rolled by one draw of
     ``cycle_spin_shifts(prior.patch_shape, prior.generator)`` in front of the levels -- what the reference's
@@ -320,6 +424,9 @@ class MultiScalePrior(Prior):
         super().__init__()
         if isinstance(prior, MultiScalePrior) or not isinstance(prior, Prior) or type(prior).device_fwd_bwd is Prior.device_fwd_bwd:
             raise ValueError("the inner prior must be a prior of jolideco_amd with a device_fwd_bwd, and not a MultiScalePrior")
+        if getattr(prior, "shift_kind", None) == "roll+jitter":
+            raise NotImplementedError(f"a MultiScalePrior around a {type(prior).__name__} is not implemented in jolideco_amd: "
+                                      "the draw of a jittered patch grid depends on each level's shape")
         if getattr(prior, "shift_kind", None) == "roll+subpixel":
             raise NotImplementedError(f"a MultiScalePrior around a {type(prior).__name__} with cycle_spin_subpix is not "
                                       "implemented in jolideco_amd: its draw (roll, offsets) is not a level's roll")

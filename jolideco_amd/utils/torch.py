@@ -11,6 +11,9 @@ __all__ = [
     "subpixel_offsets",
     "subpixel_offsets_many",
     "subpixel_kernel",
+    "jitter_grid",
+    "jitter_stride_check",
+    "jitter_draws",
     "get_default_generator",
     "view_as_overlapping_patches_torch",
 ]
@@ -94,6 +97,70 @@ def subpixel_kernel(x0, y0):
     dy = torch.abs(y - y0)
     dy = torch.where(dy < 1, 1 - dy, 0)
     return dx * dy
+
+
+def _jitter_axis(n, patch, stride):
+    """(base positions, safe) along one axis of length n: ``arange(overlap, n - stride - overlap, stride)``, and whether the
+    largest draw keeps the last patch inside, ``max(base) + overlap <= n - patch``."""
+    overlap = patch - stride
+    base = list(range(overlap, n - stride - overlap, stride))
+    return base, bool(base) and base[-1] + overlap <= n - patch
+
+
+def jitter_stride_check(patch, stride):
+    """``int(stride)`` where a jittered patch grid of ``patch`` x ``patch`` patches can be safe at it: in [patch / 2, patch].
+    ValueError otherwise -- outside [1, patch] there is no grid, and below half a patch a draw of +overlap pushes the last
+    patch of EVERY image height and width outside (the reference's own jitter test, stride 3 on 37 x 37, is such a case)."""
+    patch, stride = int(patch), int(stride)
+    if not 1 <= stride <= patch:
+        raise ValueError(f"a jittered patch grid needs a stride in [1, {patch}], got {stride}")
+    if 2 * stride < patch:
+        raise ValueError(
+            f"a jittered patch grid of {patch} x {patch} patches at stride {stride}: no image height or width is safe at this "
+            f"stride -- with overlap {patch - stride} > stride a draw can push the last patch of any axis outside the image; "
+            f"the stride must be at least {(patch + 1) // 2} (half a patch)"
+        )
+    return stride
+
+
+def jitter_grid(shape, patch_shape, stride):
+    """Base positions ``(base_y, base_x)`` (int64 tensors) of the jittered patch grid of an image of ``shape`` --
+    jolideco/utils/torch.py:299-302: ``arange(overlap, n - stride - overlap, stride)`` with ``overlap = patch - stride``; patch
+    (i, j) is cut at ``(base_y[i] + jitter_y[i], base_x[j] + jitter_x[j])`` with draws in [-overlap, overlap].
+
+    The reference keeps nothing inside the image and fails with an IndexError on an unlucky draw.  Here a shape is refused
+    up front with a ValueError unless it has a patch along both axes and NO draw can push one outside:
+    ``max(base) + overlap <= n - patch`` (for the default stride of half a patch: n a multiple of the stride).  A safe axis
+    has ``overlap <= stride`` -- the last base position L obeys ``L + stride >= n - stride - overlap`` and
+    ``L + overlap <= n - patch`` -- so below half a patch NO length is safe, and such a stride is refused whatever the shape
+    (`jitter_stride_check`); from half a patch on, ``n = L + overlap + patch`` is safe for every L of the grid (at overlap 0
+    the ``arange`` stops short of it: every n > patch is safe)."""
+    patch = max(patch_shape)
+    stride = jitter_stride_check(patch, stride)
+    bases = []
+    for axis, n in (("height", int(shape[-2])), ("width", int(shape[-1]))):
+        base, safe = _jitter_axis(n, patch, stride)
+        if not safe:
+            below = next((m for m in range(n - 1, 0, -1) if _jitter_axis(m, patch, stride)[1]), None)
+            # (2 stride >= patch: a safe length exists within a stride above n, or is the smallest one, at most 3 patches)
+            above = next((m for m in range(n + 1, n + 4 * patch + 2) if _jitter_axis(m, patch, stride)[1]), None)
+            what = "has no jittered patch" if not base else "lets a draw push a patch outside the image"
+            near = " or ".join(str(m) for m in (below, above) if m is not None) or "not within four patches"
+            raise ValueError(
+                f"the {axis} {n} of an image of shape {tuple(int(v) for v in shape[-2:])} {what} at patch size {patch} and "
+                f"stride {stride}: the nearest safe {axis} is {near}"
+            )
+        bases.append(torch.tensor(base, dtype=torch.int64))
+    return bases[0], bases[1]
+
+
+def jitter_draws(generator, n_x, n_y, overlap):
+    """The draws of one jittered evaluation exactly like jolideco/utils/torch.py:304-318: two `randint` calls in
+    [-overlap, overlap] from a HOST generator, ``(n_x,)`` FIRST, then ``(n_y,)`` -- both made when ``overlap == 0`` too
+    (the generator advances).  Returns ``(jitter_x, jitter_y)``, int64 tensors."""
+    jitter_x = torch.randint(low=-overlap, high=overlap + 1, size=(n_x,), generator=generator)
+    jitter_y = torch.randint(low=-overlap, high=overlap + 1, size=(n_y,), generator=generator)
+    return jitter_x, jitter_y
 
 
 def cycle_spin(image, patch_shape, generator):
