@@ -578,7 +578,6 @@ static int direct_template_kc(int kw, int split) { return split ? 32 * direct_sp
 static int direct_ox_in(int kw, int ox, int adjoint) { return adjoint ? -ox : ox - (kw - 1); }  // adjoint: (kw - 1 - ox) - (kw - 1)
 // the window columns of every tile start on a 16-byte boundary of the image rows
 static bool direct_stage_vec_shape(int W, int ox_in) { return W % 4 == 0 && ox_in % 4 == 0; }
-static bool is_aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }  // (null is)
 
 void direct_conv_route(int W, int kw, int ox, int split, int* route4) {
   route4[0] = direct_template_kc(kw, split);
@@ -621,12 +620,12 @@ static int launch_kc(DirectConvArgs a, hipStream_t stream) {
   }
   int grid = g_conv_n_cu * per_cu;
   if (grid > n_tiles) grid = n_tiles;
-  const bool vec = direct_stage_vec_shape(a.W, a.ox_in) && is_aligned16(a.in) && is_aligned16(a.in_scale);
+  const bool vec = direct_stage_vec_shape(a.W, a.ox_in) && aligned16(a.in) && aligned16(a.in_scale);
   // The epilogue moves float4 too, whichever way the window was staged: the gradient image of a fit's second flux
   // component is a slice of one flat buffer and only 4-byte aligned when the first component's pixel count is no
   // multiple of 4 -- such a launch takes the epilogue's element-wise branch (the same arithmetic, the same bits).
-  a.epi_vec = a.W % 4 == 0 && is_aligned16(a.out) && is_aligned16(a.out_scale) && is_aligned16(a.background) && is_aligned16(a.counts) &&
-              is_aligned16(a.npred_out);
+  a.epi_vec = a.W % 4 == 0 && aligned16(a.out) && aligned16(a.out_scale) && aligned16(a.background) && aligned16(a.counts) &&
+              aligned16(a.npred_out);
   if (vec)
     direct_conv_kernel<KC, true, POISSON, SPLIT><<<grid, 256, lds, stream>>>(a);
   else

@@ -256,7 +256,7 @@ static int bucketed_backward(jd_gmm* g, const float* flux, const PatchGrid& grid
   return JD_OK;
 }
 
-static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride, int shift_y,
+static int gmm_prior_impl(jd_gmm* g, const ImageNormArgs& norm, const float* flux, int H, int W, int stride, int shift_y,
                           int shift_x, int patch_row_begin, int patch_row_end, int marginalize,
                           float value_scale, float* value_out, int accumulate_value, float grad_coef,
                           float* grad_flux_accum, int32_t* argmax_out, float* band_out, void* stream,
@@ -271,8 +271,7 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
   JD_REQUIRE(patch_row_begin >= 0 && patch_row_begin <= patch_row_end && patch_row_end <= nPy,
              "jd_gmm_prior_fwd_bwd: patch row range [%d, %d) outside [0, %d]", patch_row_begin, patch_row_end, nPy);
   hipStream_t s = as_stream(stream);
-  shift_y = ((shift_y % H) + H) % H;  // roll by any integer = roll by its residue (the kernels' wrap() relies on it)
-  shift_x = ((shift_x % W) + W) % W;
+  shift_y = roll_residue(shift_y, H), shift_x = roll_residue(shift_x, W);
   const int n_begin = patch_row_begin * nPx, n_end = patch_row_end * nPx;
   if (n_begin == n_end) {  // empty shard: contributes nothing (an empty band has no rows)
     if (!accumulate_value) JD_HIP(hipMemsetAsync(value_out, 0, sizeof(float), s));
@@ -292,7 +291,6 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
   // the two halves may sit on different streams: the caller runs the first beside the likelihood launches of the step (it
   // does not touch the gradient image) and joins the streams in front of the second (jolideco_amd/core.py).
   bool screened = false, fused = false, lse_screened = false;
-  const ImageNormArgs norm = g->norm;
   const bool has_norm = norm.kind != NORM_IDENTITY;
   // The standardized patch norm takes the dense kernels only: the screen's error bounds are those of mean-free patches.
   const int patch_norm = g->patch_norm;
@@ -393,24 +391,23 @@ static int gmm_prior_impl(jd_gmm* g, const float* flux, int H, int W, int stride
   ga.band = band_out;
   ga.norm = norm, ga.raw_flux = raw_flux;
   if (fused) ga.winner = g->fused.winner.ptr, ga.grec = g->fused.grec.ptr, ga.flag = g->screen.ctl.ptr, ga.gen = g->screen.gen;
-  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
-  ga.vec = W % 4 == 0 && aligned(grad_flux_accum) && (!has_norm || aligned(raw_flux)) ? 1 : 0;
+  ga.vec = W % 4 == 0 && aligned16(grad_flux_accum) && (!has_norm || aligned16(raw_flux)) ? 1 : 0;
   if (step) {
     ga.do_step = 1, ga.step = *step, ga.y_begin = 0, ga.y_end = H;  // every pixel of the image takes the step
     ga.preload = opt_value(OPT_GMM_GATHER_PRELOAD, 1) != 0;
-    ga.vec = ga.vec && aligned(step->theta) && aligned(step->flux_in) && aligned(step->flux_out) && aligned(step->grad_flux) &&
-             aligned(step->m) && aligned(step->v) && aligned(step->mask);
-    for (int k = 0; k < ADDEND_MAX; ++k) ga.vec = ga.vec && aligned(step->addend[k]);
+    ga.vec = ga.vec && aligned16(step->theta) && aligned16(step->flux_in) && aligned16(step->flux_out) &&
+             aligned16(step->grad_flux) && aligned16(step->m) && aligned16(step->v) && aligned16(step->mask);
+    for (int k = 0; k < ADDEND_MAX; ++k) ga.vec = ga.vec && aligned16(step->addend[k]);
   }
   return launch_gather(ga, s);
 }
 
-extern "C" int jd_gmm_prior_fwd_bwd(jd_gmm* g, const float* flux, int H, int W, int stride, int shift_y,
-                                    int shift_x, int patch_row_begin, int patch_row_end, int marginalize,
-                                    float value_scale, float* value_out, int accumulate_value, float grad_coef,
-                                    float* grad_flux_accum, int32_t* argmax_out, const int* shift_dev, int phases,
-                                    void* stream) {
-  if (g && g->d256) {  // 16x16 patches: the whole-image pass of gmm256.hip, or a refusal
+// jd_gmm_prior_fwd_bwd under the image norm `norm`: 16x16 patches take the whole-image pass of gmm256.hip, or a refusal
+static int gmm_prior_pass(jd_gmm* g, const ImageNormArgs& norm, const float* flux, int H, int W, int stride, int shift_y,
+                          int shift_x, int patch_row_begin, int patch_row_end, int marginalize, float value_scale,
+                          float* value_out, int accumulate_value, float grad_coef, float* grad_flux_accum, int32_t* argmax_out,
+                          const int* shift_dev, int phases, void* stream) {
+  if (g->d256) {
     JD_REQUIRE(flux && value_out, "jd_gmm_prior_fwd_bwd: null argument");
     JD_REQUIRE(phases == 3, "jd_gmm_prior_fwd_bwd: D = 256 handles run whole passes only (phases = %d, need 3)", phases);
     JD_REQUIRE(H >= 16 && W >= 16 && stride >= 1, "jd_gmm_prior_fwd_bwd: image (%d, %d) / stride %d not valid for D = 256", H, W, stride);
@@ -419,7 +416,6 @@ extern "C" int jd_gmm_prior_fwd_bwd(jd_gmm* g, const float* flux, int H, int W, 
                "jd_gmm_prior_fwd_bwd: D = 256 handles take no patch row shard ([%d, %d) of %d rows)", patch_row_begin,
                patch_row_end, nPy256);
     hipStream_t s = as_stream(stream);
-    const ImageNormArgs norm = g->norm;
     const float* image = flux;
     if (norm.kind != NORM_IDENTITY) {
       int rc;
@@ -430,9 +426,27 @@ extern "C" int jd_gmm_prior_fwd_bwd(jd_gmm* g, const float* flux, int H, int W, 
     return gmm256_prior(g->d256, image, flux, norm, H, W, stride, shift_y, shift_x, marginalize, value_scale, value_out,
                         accumulate_value, grad_coef, grad_flux_accum, argmax_out, shift_dev, s, g->patch_norm);
   }
-  return gmm_prior_impl(g, flux, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, value_scale,
+  return gmm_prior_impl(g, norm, flux, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, value_scale,
                         value_out, accumulate_value, grad_coef, grad_flux_accum, argmax_out, nullptr, stream, nullptr, shift_dev,
                         phases);
+}
+
+int jd::gmm_prior_whole(jd_gmm* g, const ImageNormArgs& norm, const float* flux, int H, int W, int stride, int shift_y,
+                        int shift_x, int marginalize, float value_scale, float* value_out, int accumulate_value,
+                        float grad_coef, float* grad_flux_accum, int32_t* argmax_out, const int* shift_dev, void* stream) {
+  return gmm_prior_pass(g, norm, flux, H, W, stride, shift_y, shift_x, 0, -1, marginalize, value_scale, value_out,
+                        accumulate_value, grad_coef, grad_flux_accum, argmax_out, shift_dev, 3, stream);
+}
+
+extern "C" int jd_gmm_prior_fwd_bwd(jd_gmm* g, const float* flux, int H, int W, int stride, int shift_y,
+                                    int shift_x, int patch_row_begin, int patch_row_end, int marginalize,
+                                    float value_scale, float* value_out, int accumulate_value, float grad_coef,
+                                    float* grad_flux_accum, int32_t* argmax_out, const int* shift_dev, int phases,
+                                    void* stream) {
+  JD_REQUIRE(g, "jd_gmm_prior_fwd_bwd: null argument");
+  return gmm_prior_pass(g, g->norm, flux, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize,
+                        value_scale, value_out, accumulate_value, grad_coef, grad_flux_accum, argmax_out, shift_dev, phases,
+                        stream);
 }
 
 extern "C" int jd_gmm_prior_fwd_bwd_step(jd_gmm* g, const float* flux, int H, int W, int stride, int shift_y, int shift_x,
@@ -453,8 +467,9 @@ extern "C" int jd_gmm_prior_fwd_bwd_step(jd_gmm* g, const float* flux, int H, in
     live = live && step->addend[k] != nullptr;
     a.addend[k] = live ? step->addend[k] : nullptr;
   }
-  return gmm_prior_impl(g, flux, H, W, stride, shift_y, shift_x, 0, -1, marginalize, value_scale, value_out, accumulate_value,
-                        grad_coef, nullptr, nullptr, nullptr, stream, &a, shift_dev, phases);
+  JD_REQUIRE(g, "jd_gmm_prior_fwd_bwd: null argument");
+  return gmm_prior_impl(g, g->norm, flux, H, W, stride, shift_y, shift_x, 0, -1, marginalize, value_scale, value_out,
+                        accumulate_value, grad_coef, nullptr, nullptr, nullptr, stream, &a, shift_dev, phases);
 }
 
 extern "C" int jd_gmm_prior_band_fwd_bwd(jd_gmm* g, const float* flux, int H, int W, int stride, int shift_y,
@@ -463,6 +478,7 @@ extern "C" int jd_gmm_prior_band_fwd_bwd(jd_gmm* g, const float* flux, int H, in
                                          float* band_out, void* stream) {
   JD_REQUIRE(!(g && g->d256), "jd_gmm_prior_band_fwd_bwd: D = 256 handles have no band output");
   JD_REQUIRE(band_out, "jd_gmm_prior_band_fwd_bwd: null band");
-  return gmm_prior_impl(g, flux, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize, value_scale,
-                        value_out, accumulate_value, grad_coef, nullptr, nullptr, band_out, stream);
+  JD_REQUIRE(g, "jd_gmm_prior_fwd_bwd: null argument");
+  return gmm_prior_impl(g, g->norm, flux, H, W, stride, shift_y, shift_x, patch_row_begin, patch_row_end, marginalize,
+                        value_scale, value_out, accumulate_value, grad_coef, nullptr, nullptr, band_out, stream);
 }

@@ -636,8 +636,7 @@ int gmm256_prior(Gmm256* g, const float* image, const float* raw_flux, const Ima
   const int n = nPy * nPx;
   const int nb = tile_halves(n, g->n_cu, g->triangular);
   const unsigned tiles = (unsigned)((n + 16 * nb - 1) / (16 * nb));
-  shift_y = ((shift_y % H) + H) % H;  // roll by any integer = roll by its residue (wrap() relies on it)
-  shift_x = ((shift_x % W) + W) % W;
+  shift_y = roll_residue(shift_y, H), shift_x = roll_residue(shift_x, W);
   int rc;
   if ((rc = grow(&g->partials, &g->partials_cap, (size_t)tiles))) return rc;
   Args256 a = base_args(g);

@@ -26,23 +26,21 @@ __global__ __launch_bounds__(256) void gmm_image_norm_kernel(const float* __rest
 }
 
 int launch_image_norm(const float* in, float* out, size_t n, const ImageNormArgs& nm, int n_cu, hipStream_t s) {
-  const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-  const size_t n4 = aligned ? n / 4 : 0;
+  const size_t n4 = aligned16(in) && aligned16(out) ? n / 4 : 0;
   const size_t items = n4 + (n - 4 * n4);
   size_t blocks = (items + 255) / 256;
   const size_t cap = (size_t)n_cu * 8;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   const unsigned gb = (unsigned)blocks;
-  switch (nm.kind) {
-    case NORM_ASINH: gmm_image_norm_kernel<NORM_ASINH><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
-    case NORM_FIXED_MAX: gmm_image_norm_kernel<NORM_FIXED_MAX><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
-    case NORM_SIGMOID: gmm_image_norm_kernel<NORM_SIGMOID><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
-    case NORM_ATAN: gmm_image_norm_kernel<NORM_ATAN><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
-    case NORM_LOG: gmm_image_norm_kernel<NORM_LOG><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
-    case NORM_POWER: gmm_image_norm_kernel<NORM_POWER><<<gb, 256, 0, s>>>(in, out, n, nm, n4); break;
-    default: JD_REQUIRE(false, "image norm kind %d has no kernel", nm.kind);
-  }
+  bool launched = false;  // (the identity has no kernel here: the callers read the flux itself)
+  dispatch_norm_kind(nm.kind, [&](auto kind) {
+    if constexpr (decltype(kind)::value != NORM_IDENTITY) {
+      gmm_image_norm_kernel<decltype(kind)::value><<<gb, 256, 0, s>>>(in, out, n, nm, n4);
+      launched = true;
+    }
+  });
+  JD_REQUIRE(launched, "image norm kind %d has no kernel", nm.kind);
   JD_LAUNCH_CHECK();
   return JD_OK;
 }
@@ -471,7 +469,7 @@ extern "C" int jd_add_rolled_bands(float* grad, int H, int W, int shift_y, int s
   JD_REQUIRE(n_bands >= 1 && n_bands <= BANDS_MAX, "jd_add_rolled_bands: %d bands not in [1, %d]", n_bands, BANDS_MAX);
   AddBandsArgs a{};
   a.grad = grad, a.bands = bands, a.chunk = chunk_floats, a.H = H, a.W = W, a.n_bands = n_bands;
-  a.shift_y = ((shift_y % H) + H) % H, a.shift_x = ((shift_x % W) + W) % W;
+  a.shift_y = roll_residue(shift_y, H), a.shift_x = roll_residue(shift_x, W);
   a.y_lo = H, a.y_hi = 0;
   for (int b = 0; b < n_bands; ++b) {
     JD_REQUIRE(y_begin[b] >= 0 && y_begin[b] <= y_end[b] && y_end[b] <= H && (size_t)(y_end[b] - y_begin[b]) * W <= chunk_floats,
@@ -495,13 +493,12 @@ extern "C" int jd_add_rolled_bands_step(int H, int W, int shift_y, int shift_x, 
   JD_REQUIRE(step->sgd || (step->exp_avg && step->exp_avg_sq), "jd_add_rolled_bands_step: Adam needs its moment images");
   JD_REQUIRE(!step->addend[0], "jd_add_rolled_bands_step: addend images are not supported (use jd_add_rolled_bands + jd_adam_step_addends)");
   JD_REQUIRE(n_bands >= 1 && n_bands <= BANDS_MAX, "jd_add_rolled_bands_step: %d bands not in [1, %d]", n_bands, BANDS_MAX);
-  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
-  JD_REQUIRE(W % 4 == 0 && aligned(step->theta) && aligned(step->flux_in) && aligned(step->flux_out) && aligned(step->grad_flux) &&
-                 aligned(step->exp_avg) && aligned(step->exp_avg_sq) && aligned(step->mask),
+  JD_REQUIRE(W % 4 == 0 && aligned16(step->theta) && aligned16(step->flux_in) && aligned16(step->flux_out) &&
+                 aligned16(step->grad_flux) && aligned16(step->exp_avg) && aligned16(step->exp_avg_sq) && aligned16(step->mask),
              "jd_add_rolled_bands_step: needs W %% 4 == 0 and 16-byte aligned images (use jd_add_rolled_bands + jd_adam_step)");
   AddBandsArgs a{};
   a.grad = nullptr, a.bands = bands, a.chunk = chunk_floats, a.H = H, a.W = W, a.n_bands = n_bands;
-  a.shift_y = ((shift_y % H) + H) % H, a.shift_x = ((shift_x % W) + W) % W;
+  a.shift_y = roll_residue(shift_y, H), a.shift_x = roll_residue(shift_x, W);
   for (int b = 0; b < n_bands; ++b) {
     JD_REQUIRE(y_begin[b] >= 0 && y_begin[b] <= y_end[b] && y_end[b] <= H && (size_t)(y_end[b] - y_begin[b]) * W <= chunk_floats,
                "jd_add_rolled_bands_step: band %d rows [%d, %d) do not fit", b, y_begin[b], y_end[b]);

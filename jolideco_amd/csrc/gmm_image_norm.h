@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "jd_adam.h"
 
 namespace jd {
@@ -56,6 +58,30 @@ __device__ __forceinline__ float image_norm_deriv(float f, const ImageNormArgs& 
     case NORM_LOG: return 1.f / f;
     case NORM_POWER: return (nm.p0 / nm.p1) * powf(f / nm.p1, nm.p0 - 1.f);
     default: return 1.f;
+  }
+}
+
+// sum * n'(f), the product rounded (NORM), or the sum itself: what the adjoint kernels of the staged passes (gmm_subpix.hip,
+// gmm_jitter.hip) add for a non-zero sum.  Each keeps its own rule for an exact zero.
+template <bool NORM>
+__device__ __forceinline__ float normed_sum(float sum, float f, const ImageNormArgs& nm) {
+#pragma clang fp contract(off)
+  return NORM ? sum * image_norm_deriv(f, nm) : sum;
+}
+
+// f(std::integral_constant<int, KIND>{}) for the NORM_* constant that equals `kind`: the host's way to the kernel
+// instantiated for it.  False for a kind outside the enum; the caller refuses in its own words.
+template <class F>
+bool dispatch_norm_kind(int kind, F&& f) {
+  switch (kind) {
+    case NORM_IDENTITY: f(std::integral_constant<int, NORM_IDENTITY>{}); return true;
+    case NORM_ASINH: f(std::integral_constant<int, NORM_ASINH>{}); return true;
+    case NORM_FIXED_MAX: f(std::integral_constant<int, NORM_FIXED_MAX>{}); return true;
+    case NORM_SIGMOID: f(std::integral_constant<int, NORM_SIGMOID>{}); return true;
+    case NORM_ATAN: f(std::integral_constant<int, NORM_ATAN>{}); return true;
+    case NORM_LOG: f(std::integral_constant<int, NORM_LOG>{}); return true;
+    case NORM_POWER: f(std::integral_constant<int, NORM_POWER>{}); return true;
+    default: return false;
   }
 }
 

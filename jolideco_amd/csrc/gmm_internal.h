@@ -693,8 +693,14 @@ struct jd_gmm {
   jd::GmmPass pass;
   jd::ImageNormArgs norm{};  // image norm the next prior call takes (jd_gmm_set_image_norm; kind 0 = identity)
   int patch_norm = jd::PATCH_NORM_SUBTRACT_MEAN;  // patch norm the next prior call takes (jd_gmm_set_patch_norm)
-  jd::DevBuf<float> normed;  // n(flux) of the pass, (H, W): what phase 1 reads in place of the flux (sub-pixel cycle spin, jitter: S)
-  jd::DevBuf<float> subpix_grad;  // sub-pixel cycle spin (gmm_subpix.hip), jitter (gmm_jitter.hip): G, the gradient with respect to S, the shape of S
+  // The image a pass cuts its patches from where that is not the flux: n(flux), (H, W), under an image norm; the staged
+  // image S of a staged pass (gmm_subpix.hip: (H, W); gmm_jitter.hip: (n_y P, n_x P)), which is normed already.
+  jd::DevBuf<float> normed;
+  jd::DevBuf<float> staged_grad;  // staged passes: G, the gradient of the inner pass with respect to S, the shape of S
+  int reserve_staged(size_t n, bool want_grad) {  // S and, for a gradient, G of a staged pass of n pixels
+    if (const int rc = normed.reserve(n)) return rc;
+    return want_grad ? staged_grad.reserve(n) : JD_OK;
+  }
   int K = 0;
   bool triangular = true;  // every P_k upper triangular -> zero blocks are skipped
   int n_cu = 256;
@@ -776,5 +782,19 @@ int screened_forward(jd_gmm* g, const GmmFwdArgs& a, hipStream_t s, int* n_parti
 // gmm_gather.hip: out = n(in) per pixel; the overlap-add of the gradient rows (tile kernel | per-pixel kernel)
 int launch_image_norm(const float* in, float* out, size_t n, const ImageNormArgs& nm, int n_cu, hipStream_t s);
 int launch_gather(const GmmGatherArgs& ga, hipStream_t s);
+// gmm.hip: the whole prior of an image under the image norm `norm` -- both patch sizes, both phases, no shard; otherwise the
+// contract of jd_gmm_prior_fwd_bwd, which is this under the handle's norm.  The staged passes run it on their staged
+// image under the identity.
+int gmm_prior_whole(jd_gmm* g, const ImageNormArgs& norm, const float* flux, int H, int W, int stride, int shift_y, int shift_x,
+                    int marginalize, float value_scale, float* value_out, int accumulate_value, float grad_coef,
+                    float* grad_flux_accum, int32_t* argmax_out, const int* shift_dev, void* stream);
+
+// f(std::bool_constant<A>{}, std::bool_constant<B>{}): the host's way to one of the four instantiations of a kernel with
+// two switches (the adjoint kernels of the staged passes: NORM, VEC)
+template <class F>
+void dispatch_bools(bool a, bool b, F&& f) {
+  if (a) b ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  else b ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
 
 }  // namespace jd

@@ -3,7 +3,7 @@
 //   patch (i, j) = rolled_normed[py_i : py_i + P, px_j : px_j + P],   py_i = overlap + i s + jitter_y[i],   px_j likewise.
 // Two streaming kernels around the unchanged pass.  The stage kernel lays the patches side by side, without overlap,
 //   S[i P + a, j P + b] = n(flux[(py_i + a - sy) mod H, (px_j + b - sx) mod W]),
-// jd_gmm_prior_fwd_bwd runs on S (shape (n_y P, n_x P), stride P, no roll, identity norm, the handle's patch norm) with its
+// gmm_prior_whole runs on S (shape (n_y P, n_x P), stride P, no roll, identity norm, the handle's patch norm) with its
 // gradient G = grad_coef d(sum v_patch)/dS going to a zeroed image, and the adjoint kernel gathers per flux pixel, with
 // (Y, X) = ((y + sy) mod H, (x + sx) mod W),
 //   grad[y, x] += n'(flux[y, x]) sum_{i: 0 <= Y - py_i < P} sum_{j: 0 <= X - px_j < P} G[i P + (Y - py_i), j P + (X - px_j)]
@@ -46,8 +46,8 @@ __global__ __launch_bounds__(256) void gmm_jitter_stage_kernel(GmmJitterArgs a) 
   const int SW = a.n_x * a.P, SH = a.n_y * a.P;
   const int c = 4 * (blockIdx.x * 64 + (threadIdx.x & 63)), r = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (r >= SH || c >= SW) return;
-  const int H = a.H, W = a.W, P = a.P;
-  const int sy = a.shift_dev ? a.shift_dev[0] : a.shift_y, sx = a.shift_dev ? a.shift_dev[1] : a.shift_x;
+  use_device_shift(a);
+  const int H = a.H, W = a.W, P = a.P, sy = a.shift_y, sx = a.shift_x;
   const int i = r / P, j = c / P;  // (c % 4 == 0 and P % 4 == 0: the four columns are one patch's)
   const int Y = jitter_pos(i, P, a.stride, a.jitter_y[i]) + (r - i * P);
   const int X = jitter_pos(j, P, a.stride, a.jitter_x[j]) + (c - j * P);
@@ -73,8 +73,7 @@ __global__ __launch_bounds__(256) void gmm_jitter_stage_kernel(GmmJitterArgs a) 
 template <bool NORM>
 __device__ __forceinline__ float jitter_add(float g, float sum, float f, const ImageNormArgs& nm) {
 #pragma clang fp contract(off)
-  if (sum == 0.f) return g;
-  return g + (NORM ? sum * image_norm_deriv(f, nm) : sum);
+  return sum == 0.f ? g : g + normed_sum<NORM>(sum, f, nm);
 }
 
 template <bool NORM, bool VEC>
@@ -83,9 +82,9 @@ __global__ __launch_bounds__(256) void gmm_jitter_adjoint_kernel(GmmJitterArgs a
   // cover lists of the tile's rows and columns: rows (columns) of S, entries beyond a list's length are 0 (a valid index)
   __shared__ int row_s[GJ_MAXC][GJ_TY], col_s[GJ_MAXC][GJ_TX];
   __shared__ int row_n[GJ_TY], col_n[GJ_TX];
-  const int H = a.H, W = a.W, P = a.P;
+  use_device_shift(a);
+  const int H = a.H, W = a.W, P = a.P, sy = a.shift_y, sx = a.shift_x;
   const int tx0 = blockIdx.x * GJ_TX, ty0 = blockIdx.y * GJ_TY;
-  const int sy = a.shift_dev ? a.shift_dev[0] : a.shift_y, sx = a.shift_dev ? a.shift_dev[1] : a.shift_x;
   const int t = threadIdx.x;
   if (t < GJ_TY + GJ_TX) {
     const bool is_row = t < GJ_TY;
@@ -168,50 +167,34 @@ extern "C" int jd_gmm_prior_jitter_fwd_bwd(jd_gmm* g, const float* flux, int H, 
   JD_REQUIRE(grid_s.y <= 65535 && grid_a.y <= 65535, "jd_gmm_prior_jitter_fwd_bwd: image %d x %d too large", H, W);
   hipStream_t s = as_stream(stream);
   int rc;
-  if ((rc = g->normed.reserve(n))) return rc;
-  if (grad_flux_accum && (rc = g->subpix_grad.reserve(n))) return rc;
+  if ((rc = g->reserve_staged(n, grad_flux_accum != nullptr))) return rc;
+  float* const S = g->normed.ptr;
+  float* const G = grad_flux_accum ? g->staged_grad.ptr : nullptr;
   const ImageNormArgs norm = g->norm;
   const bool has_norm = norm.kind != NORM_IDENTITY;
-  float* const G = grad_flux_accum ? g->subpix_grad.ptr : nullptr;
 
+  // stage: S = the patches of n(flux) side by side, G = 0
   GmmJitterArgs a{};
-  a.flux = flux, a.S = g->normed.ptr, a.G = G, a.grad = grad_flux_accum, a.jitter_y = jitter_y_dev, a.jitter_x = jitter_x_dev;
+  a.flux = flux, a.S = S, a.G = G, a.grad = grad_flux_accum, a.jitter_y = jitter_y_dev, a.jitter_x = jitter_x_dev;
   a.H = H, a.W = W, a.P = patch, a.stride = stride, a.n_y = n_y, a.n_x = n_x;
-  a.shift_y = ((shift_y % H) + H) % H, a.shift_x = ((shift_x % W) + W) % W, a.shift_dev = shift_dev;
+  a.shift_y = roll_residue(shift_y, H), a.shift_x = roll_residue(shift_x, W), a.shift_dev = shift_dev;
   a.norm = norm;
-  switch (norm.kind) {
-    case NORM_IDENTITY: gmm_jitter_stage_kernel<NORM_IDENTITY><<<grid_s, 256, 0, s>>>(a); break;
-    case NORM_ASINH: gmm_jitter_stage_kernel<NORM_ASINH><<<grid_s, 256, 0, s>>>(a); break;
-    case NORM_FIXED_MAX: gmm_jitter_stage_kernel<NORM_FIXED_MAX><<<grid_s, 256, 0, s>>>(a); break;
-    case NORM_SIGMOID: gmm_jitter_stage_kernel<NORM_SIGMOID><<<grid_s, 256, 0, s>>>(a); break;
-    case NORM_ATAN: gmm_jitter_stage_kernel<NORM_ATAN><<<grid_s, 256, 0, s>>>(a); break;
-    case NORM_LOG: gmm_jitter_stage_kernel<NORM_LOG><<<grid_s, 256, 0, s>>>(a); break;
-    case NORM_POWER: gmm_jitter_stage_kernel<NORM_POWER><<<grid_s, 256, 0, s>>>(a); break;
-    default: JD_REQUIRE(false, "jd_gmm_prior_jitter_fwd_bwd: image norm kind %d has no kernel", norm.kind);
-  }
+  const bool known = dispatch_norm_kind(
+      norm.kind, [&](auto kind) { gmm_jitter_stage_kernel<decltype(kind)::value><<<grid_s, 256, 0, s>>>(a); });
+  JD_REQUIRE(known, "jd_gmm_prior_jitter_fwd_bwd: image norm kind %d has no kernel", norm.kind);
   JD_LAUNCH_CHECK();
 
-  // the unchanged pass on S: the patches lie on a regular grid of stride P; identity norm (S is normed already; the chain
-  // rule of n is the adjoint kernel's), the handle's patch norm; the handle's norm is put back whatever the pass returns
-  g->norm = ImageNormArgs{};
-  rc = jd_gmm_prior_fwd_bwd(g, g->normed.ptr, SH, SW, patch, 0, 0, 0, -1, marginalize, value_scale, value_out,
-                            accumulate_value, grad_coef, G, argmax_out, nullptr, 3, stream);
-  g->norm = norm;
+  // pass: the whole prior on S, whose patches lie on a regular grid of stride P, under the identity (S is normed already;
+  // the chain rule of n is the adjoint kernel's), the handle's patch norm, no roll
+  rc = gmm_prior_whole(g, ImageNormArgs{}, S, SH, SW, patch, 0, 0, marginalize, value_scale, value_out, accumulate_value,
+                       grad_coef, G, argmax_out, nullptr, stream);
   if (rc || !G) return rc;
 
-  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
-  const bool vec = W % 4 == 0 && aligned(grad_flux_accum) && (!has_norm || aligned(flux));
-  if (has_norm) {
-    if (vec)
-      gmm_jitter_adjoint_kernel<true, true><<<grid_a, 256, 0, s>>>(a);
-    else
-      gmm_jitter_adjoint_kernel<true, false><<<grid_a, 256, 0, s>>>(a);
-  } else {
-    if (vec)
-      gmm_jitter_adjoint_kernel<false, true><<<grid_a, 256, 0, s>>>(a);
-    else
-      gmm_jitter_adjoint_kernel<false, false><<<grid_a, 256, 0, s>>>(a);
-  }
+  // adjoint: the caller's gradient += n'(flux) * the sum of G over the patches that cover the pixel
+  const bool vec = W % 4 == 0 && aligned16(grad_flux_accum) && (!has_norm || aligned16(flux));
+  dispatch_bools(has_norm, vec, [&](auto with_norm, auto with_vec) {
+    gmm_jitter_adjoint_kernel<decltype(with_norm)::value, decltype(with_vec)::value><<<grid_a, 256, 0, s>>>(a);
+  });
   JD_LAUNCH_CHECK();
   return JD_OK;
 }

@@ -1,7 +1,7 @@
 // Sub-pixel cycle spin of the GMM patch prior (jolideco/priors/patches/core.py:189-246 with `cycle_spin_subpix`;
 // utils/torch.py:31-38,91-143): the prior is evaluated on s = conv2d(roll(n(flux)), k, "same"), the 3 x 3 cross-correlation
 // of the rolled, normed image with the bilinear weights of a shift (x0, y0) in [-0.5, 0.5]^2, ZERO outside the rolled
-// image.  Two streaming kernels around the unchanged pass (jd_gmm_prior_fwd_bwd on the staged image, identity norm, same
+// image.  Two streaming kernels around the unchanged pass (gmm_prior_whole on the staged image under the identity norm, same
 // roll).  With (Y, X) = ((y + sy) mod H, (x + sx) mod W) the rolled position of pixel (y, x):
 //
 //   stage    S[y, x]     = sum_{a,b in {-1,0,1}} k[a+1][b+1] n[(y+a) mod H, (x+b) mod W] [0 <= Y+a < H] [0 <= X+b < W]
@@ -71,10 +71,9 @@ __device__ __forceinline__ void subpix_load_window(float (&L)[GS_LH][GS_LW], con
   }
 }
 
-// the roll and the offsets of the launch (device memory first) and the nine weights
-__device__ __forceinline__ void subpix_scalars(const GmmSubpixArgs& a, int& sy, int& sx, float (&k)[3][3]) {
-  sy = a.shift_dev ? a.shift_dev[0] : a.shift_y;
-  sx = a.shift_dev ? a.shift_dev[1] : a.shift_x;
+// the roll of the launch into the kernel's own copy of its arguments, and the nine weights of its offsets (device memory first)
+__device__ __forceinline__ void subpix_scalars(GmmSubpixArgs& a, float (&k)[3][3]) {
+  use_device_shift(a);
   subpix_weights(a.offset_dev ? a.offset_dev[0] : a.x0, a.offset_dev ? a.offset_dev[1] : a.y0, k);
 }
 
@@ -84,9 +83,9 @@ __global__ __launch_bounds__(256) void gmm_subpix_stage_kernel(GmmSubpixArgs a) 
   __shared__ float L[GS_LH][GS_LW];
   const int H = a.H, W = a.W;
   const int tx0 = blockIdx.x * GS_TX, ty0 = blockIdx.y * GS_TY;
-  int sy, sx;
   float k[3][3];
-  subpix_scalars(a, sy, sx, k);
+  subpix_scalars(a, k);
+  const int sy = a.shift_y, sx = a.shift_x;
   const ImageNormArgs nm = a.norm;
   subpix_load_window<VEC>(L, a.src, H, W, tx0, ty0, [&](float f) { return image_norm_value<KIND>(f, nm); });
   __syncthreads();
@@ -124,8 +123,7 @@ __global__ __launch_bounds__(256) void gmm_subpix_stage_kernel(GmmSubpixArgs a) 
 template <bool NORM>
 __device__ __forceinline__ float subpix_normed_term(float sum, float f, const ImageNormArgs& nm) {
 #pragma clang fp contract(off)
-  if (sum == 0.f) return 0.f;
-  return NORM ? sum * image_norm_deriv(f, nm) : sum;
+  return sum == 0.f ? 0.f : normed_sum<NORM>(sum, f, nm);
 }
 
 template <bool NORM, bool VEC>
@@ -134,9 +132,9 @@ __global__ __launch_bounds__(256) void gmm_subpix_adjoint_kernel(GmmSubpixArgs a
   __shared__ float L[GS_LH][GS_LW];
   const int H = a.H, W = a.W;
   const int tx0 = blockIdx.x * GS_TX, ty0 = blockIdx.y * GS_TY;
-  int sy, sx;
   float k[3][3];
-  subpix_scalars(a, sy, sx, k);
+  subpix_scalars(a, k);
+  const int sy = a.shift_y, sx = a.shift_x;
   subpix_load_window<VEC>(L, a.src, H, W, tx0, ty0, [](float g) { return g; });
   __syncthreads();
   const int c4 = threadIdx.x & 15, r0 = threadIdx.x >> 4;
@@ -175,14 +173,6 @@ __global__ __launch_bounds__(256) void gmm_subpix_adjoint_kernel(GmmSubpixArgs a
   }
 }
 
-template <int KIND>
-static void launch_stage(const GmmSubpixArgs& a, bool vec, dim3 grid, hipStream_t s) {
-  if (vec)
-    gmm_subpix_stage_kernel<KIND, true><<<grid, 256, 0, s>>>(a);
-  else
-    gmm_subpix_stage_kernel<KIND, false><<<grid, 256, 0, s>>>(a);
-}
-
 }  // namespace jd
 
 using namespace jd;
@@ -203,52 +193,40 @@ extern "C" int jd_gmm_prior_subpix_fwd_bwd(jd_gmm* g, const float* flux, int H, 
   hipStream_t s = as_stream(stream);
   const size_t n = (size_t)H * W;
   int rc;
-  if ((rc = g->normed.reserve(n))) return rc;
-  if (grad_flux_accum && (rc = g->subpix_grad.reserve(n))) return rc;
-  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
+  if ((rc = g->reserve_staged(n, grad_flux_accum != nullptr))) return rc;
+  float* const S = g->normed.ptr;
+  float* const G = grad_flux_accum ? g->staged_grad.ptr : nullptr;
   const ImageNormArgs norm = g->norm;
   const bool has_norm = norm.kind != NORM_IDENTITY;
 
+  // stage: S = the stencil of n(flux)
   GmmSubpixArgs a{};
-  a.H = H, a.W = W, a.shift_y = ((shift_y % H) + H) % H, a.shift_x = ((shift_x % W) + W) % W, a.shift_dev = shift_dev;
+  a.H = H, a.W = W, a.shift_y = roll_residue(shift_y, H), a.shift_x = roll_residue(shift_x, W), a.shift_dev = shift_dev;
   a.x0 = x0, a.y0 = y0, a.offset_dev = offset_dev, a.norm = norm;
-  a.src = flux, a.dst = g->normed.ptr;
-  const bool vec_stage = W % 4 == 0 && aligned(flux) && aligned(g->normed.ptr);
-  switch (norm.kind) {
-    case NORM_IDENTITY: launch_stage<NORM_IDENTITY>(a, vec_stage, grid, s); break;
-    case NORM_ASINH: launch_stage<NORM_ASINH>(a, vec_stage, grid, s); break;
-    case NORM_FIXED_MAX: launch_stage<NORM_FIXED_MAX>(a, vec_stage, grid, s); break;
-    case NORM_SIGMOID: launch_stage<NORM_SIGMOID>(a, vec_stage, grid, s); break;
-    case NORM_ATAN: launch_stage<NORM_ATAN>(a, vec_stage, grid, s); break;
-    case NORM_LOG: launch_stage<NORM_LOG>(a, vec_stage, grid, s); break;
-    case NORM_POWER: launch_stage<NORM_POWER>(a, vec_stage, grid, s); break;
-    default: JD_REQUIRE(false, "jd_gmm_prior_subpix_fwd_bwd: image norm kind %d has no kernel", norm.kind);
-  }
+  a.src = flux, a.dst = S;
+  const bool vec_stage = W % 4 == 0 && aligned16(flux) && aligned16(S);
+  const bool known = dispatch_norm_kind(norm.kind, [&](auto kind) {
+    if (vec_stage)
+      gmm_subpix_stage_kernel<decltype(kind)::value, true><<<grid, 256, 0, s>>>(a);
+    else
+      gmm_subpix_stage_kernel<decltype(kind)::value, false><<<grid, 256, 0, s>>>(a);
+  });
+  JD_REQUIRE(known, "jd_gmm_prior_subpix_fwd_bwd: image norm kind %d has no kernel", norm.kind);
   JD_LAUNCH_CHECK();
 
-  // the unchanged pass on S: identity norm (S is normed already; the chain rule of n is the adjoint kernel's), the handle's
-  // patch norm, the same roll; the handle's norm is put back whatever the pass returns
-  float* const G = grad_flux_accum ? g->subpix_grad.ptr : nullptr;
+  // pass: the whole prior on S under the identity (S is normed already; the chain rule of n is the adjoint kernel's), the
+  // handle's patch norm, the same roll; its gradient goes to the zeroed G
   if (G) JD_HIP(hipMemsetAsync(G, 0, n * sizeof(float), s));
-  g->norm = ImageNormArgs{};
-  rc = jd_gmm_prior_fwd_bwd(g, g->normed.ptr, H, W, stride, shift_y, shift_x, 0, -1, marginalize, value_scale, value_out,
-                            accumulate_value, grad_coef, G, argmax_out, shift_dev, 3, stream);
-  g->norm = norm;
+  rc = gmm_prior_whole(g, ImageNormArgs{}, S, H, W, stride, shift_y, shift_x, marginalize, value_scale, value_out,
+                       accumulate_value, grad_coef, G, argmax_out, shift_dev, stream);
   if (rc || !G) return rc;
 
+  // adjoint: the caller's gradient += n'(flux) * the transposed stencil of G
   a.src = G, a.dst = grad_flux_accum, a.raw_flux = flux;
-  const bool vec = W % 4 == 0 && aligned(G) && aligned(grad_flux_accum) && (!has_norm || aligned(flux));
-  if (has_norm) {
-    if (vec)
-      gmm_subpix_adjoint_kernel<true, true><<<grid, 256, 0, s>>>(a);
-    else
-      gmm_subpix_adjoint_kernel<true, false><<<grid, 256, 0, s>>>(a);
-  } else {
-    if (vec)
-      gmm_subpix_adjoint_kernel<false, true><<<grid, 256, 0, s>>>(a);
-    else
-      gmm_subpix_adjoint_kernel<false, false><<<grid, 256, 0, s>>>(a);
-  }
+  const bool vec = W % 4 == 0 && aligned16(G) && aligned16(grad_flux_accum) && (!has_norm || aligned16(flux));
+  dispatch_bools(has_norm, vec, [&](auto with_norm, auto with_vec) {
+    gmm_subpix_adjoint_kernel<decltype(with_norm)::value, decltype(with_vec)::value><<<grid, 256, 0, s>>>(a);
+  });
   JD_LAUNCH_CHECK();
   return JD_OK;
 }

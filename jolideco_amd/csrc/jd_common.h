@@ -46,6 +46,12 @@ inline int fail(int status, const char* fmt, ...) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// May `p` be read and written in 16-byte accesses?  (Null is: an image a launch does not use stands in nobody's way.)
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// s mod n in [0, n) for any integer s: a roll by s is a roll by its residue (the kernels' wrap() relies on the range)
+inline int roll_residue(int s, int n) { return ((s % n) + n) % n; }
+
 // wave64 reductions ------------------------------------------------------------------------
 __device__ inline double wave_sum(double v) {
 #pragma unroll

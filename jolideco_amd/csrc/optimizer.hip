@@ -273,10 +273,9 @@ static int launch_step(int kind, const OptArgs& o, hipStream_t stream) {
   int na = 0;
   while (na < ADDEND_MAX && a.addend[na]) ++na;
   // float4 accesses: every image the kernel touches is 16-byte aligned (null images count as aligned), else pixel by pixel
-  auto aligned = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
-  bool vec = (a.n % 4 == 0) && aligned(a.theta) && aligned(a.flux_in) && aligned(a.flux_out) && aligned(a.grad_flux) &&
-             aligned(a.m) && aligned(a.v) && aligned(o.s) && aligned(a.mask);
-  for (int k = 0; k < na; ++k) vec = vec && aligned(a.addend[k]);
+  bool vec = (a.n % 4 == 0) && aligned16(a.theta) && aligned16(a.flux_in) && aligned16(a.flux_out) && aligned16(a.grad_flux) &&
+             aligned16(a.m) && aligned16(a.v) && aligned16(o.s) && aligned16(a.mask);
+  for (int k = 0; k < na; ++k) vec = vec && aligned16(a.addend[k]);
   const size_t per_block = (size_t)OPT_BLOCK * (vec ? 4 : 1);
   size_t count = (a.n + per_block - 1) / per_block;
   if (count > OPT_MAX_BLOCKS) count = OPT_MAX_BLOCKS;

@@ -632,9 +632,8 @@ int launch_sep(SepArgs a, int kh, int kw, int oy, int ox, int adjoint, bool pois
     if (want > lds && want <= 160 * 1024) lds = want;
   }
   const int blocks = ((a.n_tiles + 7) / 8) * 8;
-  auto aligned = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  bool vec = a.W % 4 == 0 && aligned(a.in) && aligned(a.in_scale) && aligned(a.out) && aligned(a.out_scale) &&
-             aligned(a.background) && aligned(a.counts) && aligned(a.npred_out);
+  bool vec = a.W % 4 == 0 && aligned16(a.in) && aligned16(a.in_scale) && aligned16(a.out) && aligned16(a.out_scale) &&
+             aligned16(a.background) && aligned16(a.counts) && aligned16(a.npred_out);
   vec = vec && (a.n_batch == 0 || batch_aligned);
   const bool in_scale = a.n_batch > 0 ? poisson : a.in_scale != nullptr;  // batches: forward scales its input, adjoint its output
   const int variant1 = (poisson ? 4 : 0) + (vec ? 2 : 0) + (in_scale ? 1 : 0);
@@ -703,10 +702,9 @@ int launch_sep_conv_poisson(const float* in, const float* in_scale, const float*
 }
 
 static bool table_aligned(const SepBatchTable& t, int n, int n_comp) {
-  auto ok = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   bool all = true;
-  for (int d = 0; d < n; ++d) all = all && ok(t.bkg[d]) && ok(t.cnt[d]);
-  for (int i = 0; i < n * n_comp; ++i) all = all && ok(t.scale[i]) && ok(t.g[i]);
+  for (int d = 0; d < n; ++d) all = all && aligned16(t.bkg[d]) && aligned16(t.cnt[d]);
+  for (int i = 0; i < n * n_comp; ++i) all = all && aligned16(t.scale[i]) && aligned16(t.g[i]);
   return all;
 }
 static bool table_rank1(const SepBatchTable& t, int entries) {

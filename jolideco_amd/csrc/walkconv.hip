@@ -1208,8 +1208,6 @@ __global__ __launch_bounds__(XG ? 64 * XW : 64) void walk_joint_kernel(JointArgs
   if (lane == 0) a.partials[(size_t)d * n_tiles + tile] = loss;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // Do the walk kernels take a launch over n datasets of (H, W) pixels at all?  Option JD_SEP_WALK: 0 never, 1 whenever
 // the operators allow (then independent of n: a batched step and the per-dataset calls it stands for choose alike and
 // agree bit for bit), unset: where they are the faster kernels -- which depends on n, so that by default a batched step

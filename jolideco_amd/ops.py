@@ -444,6 +444,30 @@ class JitterRing:
         self.events[slot].record()
         self.used[slot] = True
 
+    def send(self, draws, counts, overlap):
+        """(device jitter_y, device jitter_x, slot) of the ``draws`` = (jitter_y, jitter_x) of a grid of ``counts`` =
+        (n_y, n_x).  Host sequences or tensors are validated (integer, the counts, in [-overlap, overlap]) and uploaded:
+        `done(slot)` behind the launch that reads them.  int32 tensors on the ring's device go as they are, with slot None
+        (nothing in them can be validated without a synchronisation: the kernels clamp)."""
+        names = ("jitter_y", "jitter_x")
+        on_device = [isinstance(j, torch.Tensor) and j.device.type == "cuda" for j in draws]
+        if all(on_device):
+            for name, j, n in zip(names, draws, counts):
+                if j.dtype != torch.int32 or not j.is_contiguous() or j.numel() != n or j.device != self.device:
+                    raise ValueError(f"{name} on the device must be a contiguous int32 tensor of {n} draws on {self.device}")
+            return draws[0], draws[1], None
+        if any(on_device):
+            raise ValueError("jitter_y and jitter_x must both be on the host or both on the device")
+        draws = [torch.as_tensor(j).reshape(-1) for j in draws]
+        for name, j, n in zip(names, draws, counts):
+            if j.dtype not in (torch.int32, torch.int64) or j.numel() != n:
+                raise ValueError(f"{name} must hold {n} integer draws (the image's patch grid at this stride), got "
+                                 f"{j.numel()} of {j.dtype}")
+            if n and (int(j.min()) < -overlap or int(j.max()) > overlap):
+                raise ValueError(f"{name} has a draw outside [-{overlap}, {overlap}]")
+        with torch.cuda.device(self.device):
+            return self.upload(*draws)
+
 
 def jitter_counts(shape, patch, stride):
     """(n_y, n_x) of the jittered patch grid (`utils.torch.jitter_grid`; raises ValueError for an unsafe shape)"""
@@ -533,6 +557,31 @@ class GmmHandle:
         validated here, sent through a pinned ring without a host synchronisation -- or int32 tensors on the flux's device,
         which the kernels read as they are (nothing can be validated without a synchronisation: they clamp).  The whole prior
         only; excludes ``subpix``.  An unsafe shape raises ValueError."""
+        if isinstance(shifts, DeviceShifts) and band_out is not None:
+            raise ValueError("device-resident shifts are not available for the band form")
+        flux, image, shift_dev = self._begin_pass(flux, stride, shifts, norm, patch_norm)
+        # (what every entry takes behind the image and in front of its outputs)
+        value = (int(bool(marginalize)), c_float(value_scale), ptr(value_out), int(accumulate_value), c_float(grad_coef))
+        outputs = (ptr(grad), ptr(argmax_out), shift_dev)
+        if jitter is None and subpix is None:
+            if band_out is None:
+                check(_hip.lib().jd_gmm_prior_fwd_bwd(*image, int(patch_rows[0]), int(patch_rows[1]), *value, *outputs,
+                                                      int(phases), stream_ptr(flux.device)))
+                return
+            if grad is not None or argmax_out is not None:
+                raise ValueError("band_out excludes grad and argmax_out")
+            return self._band_pass(flux, image, patch_rows, value, band_out)
+        if band_out is not None or phases != 3 or tuple(patch_rows) != (0, -1) or (jitter is not None and subpix is not None):
+            what = "a jittered patch grid" if jitter is not None else "a sub-pixel cycle spin"
+            raise ValueError(f"{what} evaluates the whole prior: no patch_rows, band_out or phases, and no second variant")
+        if jitter is not None:
+            return self._jitter_pass(flux, image, jitter, value, outputs)
+        return self._subpix_pass(flux, image, subpix, value, outputs)
+
+    def _begin_pass(self, flux, stride, shifts, norm, patch_norm):
+        """What every prior entry begins with: the norms of the call go to the handle, the flux is one HIP image, the roll is
+        a host pair and, for `DeviceShifts`, a device address the kernels read instead.  Returns the contiguous flux, the
+        leading arguments (handle, flux, H, W, stride, shift_y, shift_x) of the entries, and that address (or None)."""
         flux = require_hip_tensor(flux, "flux")
         self.set_image_norm(norm)
         self.set_patch_norm(patch_norm)
@@ -541,103 +590,49 @@ class GmmHandle:
             raise ValueError("flux must be a single (H, W) image")
         shift_dev = None
         if isinstance(shifts, DeviceShifts):  # the kernels read the roll from device memory (captured graphs)
-            if band_out is not None:
-                raise ValueError("device-resident shifts are not available for the band form")
             shift_dev, shifts = ptr(shifts.dev), shifts.host
         sy, sx = (0, 0) if shifts is None else shifts
-        if jitter is not None:
-            if subpix is not None or band_out is not None or phases != 3 or tuple(patch_rows) != (0, -1):
-                raise ValueError("a jittered patch grid evaluates the whole prior: no subpix, patch_rows, band_out or phases")
-            patch = 8 if self.D == 64 else 16
-            n_y, n_x = jitter_counts((H, W), patch, stride)
-            overlap = patch - int(stride)
-            jitter_y, jitter_x = jitter
-            on_device = [isinstance(j, torch.Tensor) and j.device.type == "cuda" for j in (jitter_y, jitter_x)]
-            slot = None
-            if all(on_device):
-                for name, j, n in (("jitter_y", jitter_y, n_y), ("jitter_x", jitter_x, n_x)):
-                    if j.dtype != torch.int32 or not j.is_contiguous() or j.numel() != n or j.device != flux.device:
-                        raise ValueError(f"{name} on the device must be a contiguous int32 tensor of {n} draws on {flux.device}")
-            elif any(on_device):
-                raise ValueError("jitter_y and jitter_x must both be on the host or both on the device")
-            else:
-                jitter_y, jitter_x = (torch.as_tensor(j).reshape(-1) for j in (jitter_y, jitter_x))
-                for name, j, n in (("jitter_y", jitter_y, n_y), ("jitter_x", jitter_x, n_x)):
-                    if j.dtype not in (torch.int32, torch.int64) or j.numel() != n:
-                        raise ValueError(f"{name} must hold {n} integer draws for a ({H}, {W}) image at stride {stride}, got "
-                                         f"{j.numel()} of {j.dtype}")
-                    if n and (int(j.min()) < -overlap or int(j.max()) > overlap):
-                        raise ValueError(f"{name} has a draw outside [-{overlap}, {overlap}]")
-                if self._jitter_ring is None:
-                    self._jitter_ring = JitterRing(flux.device)
-                with torch.cuda.device(flux.device):
-                    jitter_y, jitter_x, slot = self._jitter_ring.upload(jitter_y, jitter_x)
-            check(
-                _hip.lib().jd_gmm_prior_jitter_fwd_bwd(
-                    self._handle, ptr(flux), H, W, int(stride), int(sy), int(sx), ptr(jitter_y), ptr(jitter_x),
-                    int(bool(marginalize)), c_float(value_scale), ptr(value_out), int(accumulate_value), c_float(grad_coef),
-                    ptr(grad), ptr(argmax_out), shift_dev, stream_ptr(flux.device),
-                )
-            )
-            if slot is not None:
-                with torch.cuda.device(flux.device):
-                    self._jitter_ring.done(slot)
-            return
-        if subpix is not None:
-            if band_out is not None or phases != 3 or tuple(patch_rows) != (0, -1):
-                raise ValueError("a sub-pixel cycle spin evaluates the whole prior: no patch_rows, band_out or phases")
-            offset_dev = None
-            if isinstance(subpix, DeviceShifts):
-                offset_dev, subpix = ptr(subpix.dev), subpix.host
-            x0, y0 = subpix
-            check(
-                _hip.lib().jd_gmm_prior_subpix_fwd_bwd(
-                    self._handle, ptr(flux), H, W, int(stride), int(sy), int(sx), c_float(x0), c_float(y0),
-                    int(bool(marginalize)), c_float(value_scale), ptr(value_out), int(accumulate_value), c_float(grad_coef),
-                    ptr(grad), ptr(argmax_out), shift_dev, offset_dev, stream_ptr(flux.device),
-                )
-            )
-            return
-        if band_out is not None:
-            if grad is not None or argmax_out is not None:
-                raise ValueError("band_out excludes grad and argmax_out")
-            y0, y1 = band_rows(patch_rows, stride, H)
-            if band_out.numel() < (y1 - y0) * W:
-                raise ValueError(f"band_out holds {band_out.numel()} values, rows [{y0}, {y1}) x {W} need {(y1 - y0) * W}")
-            check(
-                _hip.lib().jd_gmm_prior_band_fwd_bwd(
-                    self._handle, ptr(flux), H, W, int(stride), int(sy), int(sx), int(patch_rows[0]), int(patch_rows[1]),
-                    int(bool(marginalize)), c_float(value_scale), ptr(value_out), int(accumulate_value),
-                    c_float(grad_coef), ptr(band_out), stream_ptr(flux.device),
-                )
-            )
-            return
-        check(
-            _hip.lib().jd_gmm_prior_fwd_bwd(
-                self._handle, ptr(flux), H, W, int(stride), int(sy), int(sx), int(patch_rows[0]), int(patch_rows[1]),
-                int(bool(marginalize)), c_float(value_scale), ptr(value_out), int(accumulate_value),
-                c_float(grad_coef), ptr(grad), ptr(argmax_out), shift_dev, int(phases), stream_ptr(flux.device),
-            )
-        )
+        return flux, (self._handle, ptr(flux), H, W, int(stride), int(sy), int(sx)), shift_dev
+
+    def _band_pass(self, flux, image, patch_rows, value, band_out):
+        H, W, stride = image[2:5]
+        y0, y1 = band_rows(patch_rows, stride, H)
+        if band_out.numel() < (y1 - y0) * W:
+            raise ValueError(f"band_out holds {band_out.numel()} values, rows [{y0}, {y1}) x {W} need {(y1 - y0) * W}")
+        check(_hip.lib().jd_gmm_prior_band_fwd_bwd(*image, int(patch_rows[0]), int(patch_rows[1]), *value, ptr(band_out),
+                                                   stream_ptr(flux.device)))
+
+    def _subpix_pass(self, flux, image, subpix, value, outputs):
+        offset_dev = None
+        if isinstance(subpix, DeviceShifts):
+            offset_dev, subpix = ptr(subpix.dev), subpix.host
+        x0, y0 = subpix
+        check(_hip.lib().jd_gmm_prior_subpix_fwd_bwd(*image, c_float(x0), c_float(y0), *value, *outputs, offset_dev,
+                                                     stream_ptr(flux.device)))
+
+    def _jitter_pass(self, flux, image, jitter, value, outputs):
+        H, W, stride = image[2:5]
+        patch = 8 if self.D == 64 else 16
+        if self._jitter_ring is None:
+            self._jitter_ring = JitterRing(flux.device)
+        ring = self._jitter_ring
+        jitter_y, jitter_x, slot = ring.send(jitter, jitter_counts((H, W), patch, stride), patch - stride)
+        check(_hip.lib().jd_gmm_prior_jitter_fwd_bwd(*image, ptr(jitter_y), ptr(jitter_x), *value, *outputs,
+                                                     stream_ptr(flux.device)))
+        if slot is not None:
+            with torch.cuda.device(flux.device):
+                ring.done(slot)
 
     def prior_fwd_bwd_step(self, flux, stride, shifts, value_out, value_scale, grad_coef, step, marginalize=False,
                            accumulate_value=False, phases=3, norm=None, patch_norm=None):
         """The whole prior with the component's optimizer step in the epilogue of its gather kernel
         (jd_gmm_prior_fwd_bwd_step; ``step``: a filled `_hip.Step`).  Raises RuntimeError where the library does not
         support it (stride < 4): the caller then evaluates the prior and steps separately."""
-        flux = require_hip_tensor(flux, "flux")
-        self.set_image_norm(norm)
-        self.set_patch_norm(patch_norm)
-        H, W = flux.shape[-2:]
-        shift_dev = None
-        if isinstance(shifts, DeviceShifts):
-            shift_dev, shifts = ptr(shifts.dev), shifts.host
-        sy, sx = (0, 0) if shifts is None else shifts
+        flux, image, shift_dev = self._begin_pass(flux, stride, shifts, norm, patch_norm)
         check(
             _hip.lib().jd_gmm_prior_fwd_bwd_step(
-                self._handle, ptr(flux), H, W, int(stride), int(sy), int(sx), int(bool(marginalize)), c_float(value_scale),
-                ptr(value_out), int(accumulate_value), c_float(grad_coef), ctypes.byref(step), shift_dev, int(phases),
-                stream_ptr(flux.device),
+                *image, int(bool(marginalize)), c_float(value_scale), ptr(value_out), int(accumulate_value),
+                c_float(grad_coef), ctypes.byref(step), shift_dev, int(phases), stream_ptr(flux.device),
             )
         )
 
@@ -712,10 +707,9 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     """Scalar GMM patch log-prior with its HIP gradient (priors/patches/core.py:227-246)."""
 
     @staticmethod
-    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None, patch_norm=None, subpix=None,
-                jitter=None):
-        """``subpix``: the offsets (x0, y0) of a sub-pixel cycle spin (None: none); ``jitter``: the draws (jitter_y, jitter_x)
-        of a jittered patch grid (None: none)."""
+    def forward(ctx, flux, handle, stride, shifts, marginalize, value_scale, norm=None, patch_norm=None, variant=None):
+        """``variant``: None, or the keyword of `GmmHandle.prior_fwd_bwd` a staged pass is reached under and its draw:
+        ("subpix", (x0, y0)) or ("jitter", (jitter_y, jitter_x))."""
         image = require_hip_tensor(flux, "flux")
         value = torch.empty(1, dtype=torch.float32, device=image.device)
         grad = None
@@ -723,7 +717,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
             grad = torch.zeros(image.shape[-2:], dtype=torch.float32, device=image.device)
         handle.prior_fwd_bwd(
             image.reshape(image.shape[-2:]), stride, shifts, value, value_scale, grad=grad, grad_coef=value_scale,
-            marginalize=marginalize, norm=norm, patch_norm=patch_norm, subpix=subpix, jitter=jitter,
+            marginalize=marginalize, norm=norm, patch_norm=patch_norm, **({} if variant is None else dict([variant])),
         )
         ctx.grad, ctx.shape = grad, flux.shape
         return value.reshape(())
@@ -731,7 +725,7 @@ class GMMPatchPriorFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_value):
         # (ctx.grad is the finished gradient with respect to the raw flux: the library applied the norm's chain rule)
-        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None, None, None, None
+        return (ctx.grad * grad_value).reshape(ctx.shape), None, None, None, None, None, None, None, None
 
 
 def elementwise_prior_subpix(kind, flux, alpha, beta, log_const, shifts, value_out, grad_coef, grad=None):

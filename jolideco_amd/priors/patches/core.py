@@ -87,19 +87,16 @@ class GMMPatchPrior(Prior):
     def patch_shape(self):
         return self.gmm.patch_shape
 
-    @property
-    def shift_kind(self):
-        """What `draw_shifts` returns: "roll" -- a pair of integer rolls or None -- or, with ``cycle_spin_subpix``,
-        "roll+subpixel": the pair (roll or None, (x0, y0)), with ``jitter`` "roll+jitter": (roll or None, (jitter_x, jitter_y))."""
-        if self.jitter:
-            return "roll+jitter"
-        return "roll+subpixel" if self.cycle_spin_subpix else "roll"
+    # What a subclass with a staged pass (a variant) sets, beside `_draw_variant` and `_order_variant`:
+    shift_kind = "roll"  # what `draw_shifts` returns: a pair of integer rolls or None; a variant: (that, the variant's draw)
+    _variant_keyword = None  # the keyword of `GmmHandle.prior_fwd_bwd` the variant's draw goes under; such a prior is whole-image only
+    _variant_form = None  # how the variant's draw is written in messages
+    _no_hessian_ones = None  # why the variant has no `hessian_ones` (None: it has)
 
     @property
     def _full_path(self):
-        """8x8 patches run every form of the pass; 16x16 patches (D = 256), a sub-pixel cycle spin and a jittered patch grid
-        have the whole-image pass only."""
-        return tuple(self.patch_shape) == (8, 8) and not self.cycle_spin_subpix and not self.jitter
+        """8x8 patches run every form of the pass; 16x16 patches (D = 256) and a variant have the whole-image pass only."""
+        return tuple(self.patch_shape) == (8, 8) and self._variant_keyword is None
 
     @property
     def shardable(self):
@@ -127,19 +124,25 @@ class GMMPatchPrior(Prior):
         """stride^2 / patch area (priors/patches/core.py:222-225)."""
         return self.stride**2 / (self.patch_shape[0] * self.patch_shape[1])
 
-    def draw_shifts(self):
-        """One pair of cycle-spin draws (None when cycle_spin is off); with ``cycle_spin_subpix`` the pair
-        (that, (x0, y0)): the roll is drawn first, then the offsets, x0 first -- the reference's order."""
+    def _draw_grid(self, shape):
+        """What the variant's draw needs to know of an image of ``shape``; a shape the variant cannot take raises here"""
+        return None
+
+    def draw_shifts(self, shape=None):
+        """One draw: the pair of cycle-spin rolls (None when cycle_spin is off); a variant returns the pair (that, its own
+        draw) -- the roll is drawn first, the reference's order.  ``shape``: the image's, for a variant whose draw depends
+        on it."""
+        grid = self._draw_grid(shape)  # (a refused shape raises before the generator advances)
         shifts = cycle_spin_shifts(self.patch_shape, self.generator) if self.cycle_spin else None
-        if self.cycle_spin_subpix:
-            shifts = (shifts, subpixel_offsets(self.generator))
+        if self._variant_keyword is not None:
+            shifts = (shifts, self._draw_variant(grid))
         self.last_shifts = shifts
         return shifts
 
-    def draw_shifts_many(self, n):
-        """The next `n` pairs of cycle-spin draws, in order (an epoch's worth, `FitSession._plan_epoch`)."""
-        if self.cycle_spin_subpix:  # (integer and float draws alternate per evaluation: one by one)
-            return [self.draw_shifts() for _ in range(n)]
+    def draw_shifts_many(self, n, shape=None):
+        """The next `n` draws, in order (an epoch's worth, `FitSession._plan_epoch`)."""
+        if self._variant_keyword is not None:  # (the roll's and the variant's draws alternate per evaluation: one by one)
+            return [self.draw_shifts(shape) for _ in range(n)]
         if not self.cycle_spin:
             self.last_shifts = None
             return [None] * n
@@ -148,43 +151,46 @@ class GMMPatchPrior(Prior):
         return shifts
 
     def __call__(self, flux, mask=None):
-        """Differentiable log-prior of a (1, 1, H, W) HIP tensor; draws one pair of shifts."""
+        """Differentiable log-prior of a (1, 1, H, W) HIP tensor; draws once, for the flux's shape."""
         from ...ops import GMMPatchPriorFunction
 
-        shifts, subpix = self._split_shifts(self.draw_shifts())
+        roll, variant = self._split_shifts(self.draw_shifts(flux.shape))
         scale = self.log_like_weight / flux.numel()
         return GMMPatchPriorFunction.apply(
-            flux, self.gmm.handle(flux.device), self.stride, shifts, self.marginalize, scale, self.norm, self.patch_norm, subpix
+            flux, self.gmm.handle(flux.device), self.stride, roll, self.marginalize, scale, self.norm, self.patch_norm,
+            None if variant is None else (self._variant_keyword, variant),
         )
 
     def _split_shifts(self, shifts):
-        """(roll, sub-pixel offsets or None) of a draw of `draw_shifts`."""
-        if not self.cycle_spin_subpix:
+        """(roll, the variant's draw as the handle takes it -- or None) of a draw of `draw_shifts`."""
+        if self._variant_keyword is None:
             return shifts, None
-        if not (isinstance(shifts, tuple) and len(shifts) == 2 and shifts[1] is not None and not isinstance(shifts[1], int)):
-            raise ValueError(f"a prior with cycle_spin_subpix takes the pair (roll or None, (x0, y0)) as shifts, got {shifts!r}")
-        return shifts
+        variant = self._order_variant(shifts[1]) if isinstance(shifts, tuple) and len(shifts) == 2 else None
+        if variant is None:
+            raise ValueError(f"a {type(self).__name__} takes the pair (roll or None, {self._variant_form}) as shifts, got {shifts!r}")
+        return shifts[0], variant
 
     def device_fwd_bwd(self, flux, value_out, grad=None, coef=0.0, patch_rows=None, shifts="draw", band_out=None, phases=3):
         """Fused path: value -> device scalar, ``grad += coef * d logprior / d flux``; with ``band_out`` the gradient of
-        the shard ``patch_rows`` goes, un-accumulated, to the band of the rolled frame it covers (sharded joint fit)."""
+        the shard ``patch_rows`` goes, un-accumulated, to the band of the rolled frame it covers (sharded joint fit).
+        ``shifts``: a draw of `draw_shifts` ("draw": one for the flux's shape).  A variant runs the whole prior only."""
         if isinstance(shifts, str):
-            shifts = self.draw_shifts()
-        shifts, subpix = self._split_shifts(shifts)
+            shifts = self.draw_shifts(flux.shape)
+        roll, variant = self._split_shifts(shifts)
         scale = self.log_like_weight / flux.numel()
         self.gmm.handle(flux.device).prior_fwd_bwd(
-            flux.reshape(flux.shape[-2:]), self.stride, shifts, value_out, scale, grad=grad, grad_coef=coef * scale,
+            flux.reshape(flux.shape[-2:]), self.stride, roll, value_out, scale, grad=grad, grad_coef=coef * scale,
             marginalize=self.marginalize, patch_rows=patch_rows or (0, -1), band_out=band_out, phases=phases, norm=self.norm,
-            patch_norm=self.patch_norm, subpix=subpix,
+            patch_norm=self.patch_norm, **({} if variant is None else {self._variant_keyword: variant}),
         )
 
     def device_fwd_bwd_step(self, flux, value_out, coef, step, shifts="draw", phases=3):
         """`device_fwd_bwd` of the WHOLE prior with the component's optimizer step applied by its gather kernel:
         ``step.grad_flux`` holds every other gradient term; theta, the moments and the new flux are written in place
         (jd_gmm_prior_fwd_bwd_step).  Same numbers as `device_fwd_bwd` followed by the stand-alone step."""
-        if self.cycle_spin_subpix:
-            raise NotImplementedError("a GMMPatchPrior with cycle_spin_subpix has no fused optimizer step: call "
-                                      "device_fwd_bwd and step separately")
+        if self._variant_keyword is not None:
+            raise NotImplementedError(f"a {type(self).__name__} has no fused optimizer step: call device_fwd_bwd and step "
+                                      "separately")
         if isinstance(shifts, str):
             shifts = self.draw_shifts()
         scale = self.log_like_weight / flux.numel()
@@ -200,18 +206,14 @@ class GMMPatchPrior(Prior):
         The argument holds for `SubtractMeanPatchNorm` only: under the standardized norm a constant added to a patch
         changes x = (p - m) / m, and there is no kernel for that Hessian product."""
         self.check_hessian_ones()
-        self.draw_shifts()
+        self.draw_shifts(flux.shape)
         return torch.zeros_like(flux)
 
     def check_hessian_ones(self):
         """Raise where `hessian_ones` (``compute_error=True``) is not available: any patch norm but subtract-mean, and a
-        sub-pixel cycle spin -- the zero-padded stencil of a constant image is not constant at the border and the seam of
-        the roll, so a constant vector is not in the null space of the patches' quadratic forms."""
-        if self.cycle_spin_subpix:
-            raise NotImplementedError(
-                "compute_error=True is not implemented for a GMMPatchPrior with cycle_spin_subpix: the Hessian product "
-                "with ones is not zero behind the zero-padded sub-pixel stencil"
-            )
+        variant that says so (`_no_hessian_ones`)."""
+        if self._no_hessian_ones:
+            raise NotImplementedError(f"compute_error=True is not implemented for a GMMPatchPrior with {self._no_hessian_ones}")
         if not isinstance(self.patch_norm, SubtractMeanPatchNorm):
             name = self.patch_norm.to_dict().get("type", type(self.patch_norm).__name__)
             raise NotImplementedError(
@@ -274,6 +276,21 @@ class SubpixelGMMPatchPrior(GMMPatchPrior):
                          jitter=jitter, marginalize=marginalize, device=device)
         self.cycle_spin_subpix = True
 
+    shift_kind = "roll+subpixel"
+    _variant_keyword = "subpix"
+    _variant_form = "(x0, y0)"
+    # (the zero-padded stencil of a constant image is not constant at the border and the seam of the roll, so a constant
+    # vector is not in the null space of the patches' quadratic forms)
+    _no_hessian_ones = "cycle_spin_subpix: the Hessian product with ones is not zero behind the zero-padded sub-pixel stencil"
+
+    def _draw_variant(self, grid):
+        """(x0, y0), x0 first"""
+        return subpixel_offsets(self.generator)
+
+    @staticmethod
+    def _order_variant(offsets):
+        return None if offsets is None or isinstance(offsets, int) else offsets
+
 
 class JitteredGMMPatchPrior(GMMPatchPrior):
     """`GMMPatchPrior` with the reference's ``jitter=True`` (jolideco/utils/torch.py:278-334): behind the norm and the roll
@@ -308,64 +325,31 @@ class JitteredGMMPatchPrior(GMMPatchPrior):
         jitter_stride_check(max(self.patch_shape), self.stride)
         self.jitter = True
 
+    shift_kind = "roll+jitter"
+    _variant_keyword = "jitter"
+    _variant_form = "(jitter_x, jitter_y)"
+
     def check_shape(self, shape):
         """(n_y, n_x) of the grid of an image of ``shape``; ValueError for a shape that is too small or not safe"""
         base_y, base_x = jitter_grid(shape, self.patch_shape, self.stride)
         return int(base_y.numel()), int(base_x.numel())
 
-    def draw_shifts(self, shape=None):
-        """One draw for an image of ``shape``: ``(roll or None, (jitter_x, jitter_y))`` -- the two roll draws, then the
-        columns' draws, then the rows', the reference's order; the jitter arrays are int64 host tensors."""
+    def _draw_grid(self, shape):
         if shape is None:
             raise ValueError("the draw of a JitteredGMMPatchPrior depends on the image: draw_shifts(shape)")
-        n_y, n_x = self.check_shape(shape)  # (an unsafe shape raises before the generator advances)
-        roll = cycle_spin_shifts(self.patch_shape, self.generator) if self.cycle_spin else None
-        self.last_shifts = (roll, jitter_draws(self.generator, n_x, n_y, self.overlap))
-        return self.last_shifts
+        return self.check_shape(shape)
 
-    def draw_shifts_many(self, n, shape=None):
-        return [self.draw_shifts(shape) for _ in range(n)]
+    def _draw_variant(self, grid):
+        """(jitter_x, jitter_y): the columns' draws, then the rows', the reference's order; int64 host tensors"""
+        n_y, n_x = grid
+        return jitter_draws(self.generator, n_x, n_y, self.overlap)
 
     @staticmethod
-    def _split(shifts):
-        """(roll, (jitter_y, jitter_x)) -- the library's order -- of a draw of `draw_shifts`"""
-        if not (isinstance(shifts, tuple) and len(shifts) == 2 and isinstance(shifts[1], (tuple, list)) and len(shifts[1]) == 2
-                and not isinstance(shifts[1][0], (int, float))):
-            raise ValueError(f"a JitteredGMMPatchPrior takes the pair (roll or None, (jitter_x, jitter_y)) as shifts, got {shifts!r}")
-        roll, (jitter_x, jitter_y) = shifts
-        return roll, (jitter_y, jitter_x)
-
-    def __call__(self, flux, mask=None):
-        """Differentiable log-prior of a (1, 1, H, W) HIP tensor; draws once for the flux's shape."""
-        from ...ops import GMMPatchPriorFunction
-
-        roll, jitter = self._split(self.draw_shifts(flux.shape))
-        scale = self.log_like_weight / flux.numel()
-        return GMMPatchPriorFunction.apply(
-            flux, self.gmm.handle(flux.device), self.stride, roll, self.marginalize, scale, self.norm, self.patch_norm, None, jitter
-        )
-
-    def device_fwd_bwd(self, flux, value_out, grad=None, coef=0.0, patch_rows=None, shifts="draw", band_out=None, phases=3):
-        """Fused path: value -> device scalar, ``grad += coef * d logprior / d flux``.  The whole prior only; ``shifts``: a
-        draw of `draw_shifts` ("draw": one for the flux's shape)."""
-        if isinstance(shifts, str):
-            shifts = self.draw_shifts(flux.shape)
-        roll, jitter = self._split(shifts)
-        scale = self.log_like_weight / flux.numel()
-        self.gmm.handle(flux.device).prior_fwd_bwd(
-            flux.reshape(flux.shape[-2:]), self.stride, roll, value_out, scale, grad=grad, grad_coef=coef * scale,
-            marginalize=self.marginalize, patch_rows=patch_rows or (0, -1), band_out=band_out, phases=phases, norm=self.norm,
-            patch_norm=self.patch_norm, jitter=jitter,
-        )
-
-    def device_fwd_bwd_step(self, flux, value_out, coef, step, shifts="draw", phases=3):
-        raise NotImplementedError("a JitteredGMMPatchPrior has no fused optimizer step: call device_fwd_bwd and step separately")
-
-    def hessian_ones(self, flux):
-        """Zero, as for the plain prior (a jittered patch still has its mean subtracted); draws once with the flux's shape."""
-        self.check_hessian_ones()
-        self.draw_shifts(flux.shape)
-        return torch.zeros_like(flux)
+    def _order_variant(jitter):
+        """(jitter_y, jitter_x): the library's order"""
+        if not (isinstance(jitter, (tuple, list)) and len(jitter) == 2 and not isinstance(jitter[0], (int, float))):
+            return None
+        return jitter[1], jitter[0]
 
     def n_patch_rows(self, shape):
         return self.check_shape(shape)[0]

@@ -193,7 +193,7 @@ def test_constructor_flags_and_refusals():
     with pytest.raises(NotImplementedError, match="fused optimizer step"):
         prior.device_fwd_bwd_step(torch.ones((16, 16)), None, 1.0, None)
     with pytest.raises(ValueError, match="pair"):
-        prior._split((1, 2))
+        prior._split_shifts((1, 2))
 
 
 def test_strides_below_half_a_patch_are_refused_by_name():
