@@ -94,9 +94,9 @@ enum JdOption {
   OPT_SEP_WALK_COLS, OPT_SEP_WALK_ROWS, OPT_SEP_WALK_ADJ_COLS, OPT_SEP_WALK_ADJ_ROWS, OPT_DIRECT_FP32,
   OPT_CONV_BLOCKS_PER_CU, OPT_POISSON_ROWS, OPT_GMM_NO_HOST_STATS, OPT_GMM_BLOCK_TILES, OPT_GMM_DENSE, OPT_GMM_KSPLIT,
   OPT_GMM_SCREEN_NO_LDS_CONSTS, OPT_GMM_SCREEN_DEBUG, OPT_GMM_SCREEN, OPT_GMM_FUSED_BWD,
-  OPT_GMM_GATHER_TILED, OPT_GMM_LSE_SCREEN, OPT_SEP_JOINT, OPT_SEP_JOINT_ROWS, OPT_SEP_JOINT_CHUNK,
-  OPT_SEP_WALK_ADJ_ALL, OPT_SEP_WALK_COST33, OPT_SEP_WALK_ROWS33, OPT_SEP_NO_TRIM, OPT_SEP_WALK_ADJ_ROWS33,
-  OPT_SEP_WALK_ADJ33, OPT_FFT_NATIVE, OPT_DIRECT_AUTO_ALL, OPT_FFT_BATCH, OPT_FFT_TINY, OPT_FFT_POOL_IO, OPT_GMM_SORT_BLOCKS, OPT_GMM_GATHER_PRELOAD,
+  OPT_GMM_GATHER_TILED, OPT_GMM_LSE_SCREEN,
+  OPT_SEP_WALK_ADJ_ALL, OPT_SEP_WALK_ROWS33, OPT_SEP_NO_TRIM, OPT_SEP_WALK_ADJ_ROWS33,
+  OPT_FFT_NATIVE, OPT_DIRECT_AUTO_ALL, OPT_FFT_BATCH, OPT_FFT_TINY, OPT_FFT_POOL_IO, OPT_GMM_SORT_BLOCKS, OPT_GMM_GATHER_PRELOAD,
   OPT_SEP_ADJ_ADDENDS, OPT_SEP_WALK_CHAIN, OPT_SEP_WALK_ADJ_CHAIN, OPT_COUNT
 };
 bool opt_is_set(int id);
@@ -212,9 +212,9 @@ int launch_sep_conv_adjoint_batch(int n, int n_comp, int comp, const SepBatchTab
 // (the batched and the per-dataset step must choose the same kernel for every dataset to stay bit-identical)
 bool sep_batch_is_mixed(int n, int n_comp, const SepBatchTable& table, int H, int W, int kh, int kw, int oy, int ox);
 
-// strip-walk form of the separable convolution (walkconv.hip; rank-1 PSFs whose non-zero taps fit a frame of 17 or 33
-// taps): same contracts as the launch_sep_* functions above; JD_WALK_NOT_TAKEN when the case is not theirs (nothing was
-// launched)
+// strip-walk form of the separable convolution (walkconv.hip, walk_adjoint.hip, walk_multi.hip; rank-1 PSFs whose
+// non-zero taps fit a frame of 17 or 33 taps): same contracts as the launch_sep_* functions above; JD_WALK_NOT_TAKEN when
+// the case is not theirs (nothing was launched)
 constexpr int JD_WALK_NOT_TAKEN = 1;
 // geometry, size and option JD_SEP_WALK only (rank-1 operators and aligned images assumed): forward and adjoint
 bool walk_takes_launch(int H, int W, int n_datasets, int kh, int kw, int oy, int ox);
@@ -231,10 +231,6 @@ int walk_conv_poisson(const float* in, const float* in_scale, const float* op, f
 int walk_conv_poisson_batch(int n, const float* flux, const SepBatchTable& table, const SepBatchTable* table_dev, int H,
                             int W, int kh, int kw, int oy, int ox, double* partials, float eps, float inv_n,
                             int write_grad, int* n_partials, hipStream_t stream);
-// forward models + Poisson passes + adjoints + the sum over the datasets of a joint step in one launch (per 8 datasets)
-int walk_joint_step(int n, const float* flux, const SepBatchTable& table, const SepBatchTable* table_dev, float* grad, int H,
-                    int W, int kh, int kw, int oy, int ox, double* partials, float eps, float inv_n, float coef,
-                    int accumulate, int* n_partials, hipStream_t stream);
 int walk_conv_poisson_batch_multi(int n, int n_comp, const float* const* flux, const SepBatchTable& table,
                                   const SepBatchTable* table_dev, int H, int W, int kh, int kw, int oy, int ox,
                                   double* partials, float eps, float inv_n, int write_grad, int* n_partials,

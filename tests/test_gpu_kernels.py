@@ -1096,13 +1096,17 @@ def test_an_operator_buffer_overwritten_behind_the_library_is_reported(jd_option
 
 
 @pytest.mark.parametrize("shape,kshape,n_obs", [((100, 260), (17, 17), 8), ((130, 300), (17, 8), 3), ((64, 128), (9, 13), 2),
-                                                ((96, 256), (5, 5), 1), ((200, 512), (16, 17), 11)],
-                         ids=["8obs", "3obs", "2obs", "1obs", "11obs"])
+                                                ((96, 256), (5, 5), 1), ((200, 512), (16, 17), 11),
+                                                ((80, 132), (33, 33), 2), ((80, 132), (33, 33), 4), ((80, 132), (33, 33), 7)],
+                         ids=["8obs", "3obs", "2obs", "1obs", "11obs", "33tap-2obs", "33tap-4obs", "33tap-7obs"])
 def test_fused_likelihood_step_equals_the_two_launch_path_bit_for_bit(jd_option, shape, kshape, n_obs):
-    """Option JD_SEP_JOINT = 1: forward model, Poisson pass, adjoint convolution and the sum over the datasets in ONE
-    launch (walk_joint_kernel: the g images are never written).  Same arithmetic in the same order as the strip-walk
-    forward + adjoint launches: the gradient of the joint step is the same bit for bit (batched and per dataset), the
-    losses are summed over other tiles and agree to rounding."""
+    """Option JD_SEP_WALK = 1 makes a batched joint step and the per-dataset calls it stands for choose the strip-walk
+    kernels alike (walk_enabled): the batched adjoint adds the datasets' rows in dataset order through its LDS exchange,
+    so the gradient of the joint step is the same bit for bit, batched and per dataset; the losses are summed by other
+    kernels and agree to rounding.  17-tap frame: one case per rung of the exchange ladder (groups of 6, 3 and 2 rows),
+    the single-dataset tail (the plain walk) and two chunks (8 + 3 datasets).  33-tap frame: groups of 2, 3 and 6 rows on
+    two strips at two columns per lane, the second ragged, and more than one tile at the smallest tile height.
+    (The name is from the one-launch kernel, since removed, that this test used to pin to this path.)"""
     from jolideco_amd.data import gaussian_kernel
     from jolideco_amd.ops import ConvPlan, stirling_mean
 
@@ -1131,13 +1135,10 @@ def test_fused_likelihood_step_equals_the_two_launch_path_bit_for_bit(jd_option,
         return grad.cpu().numpy(), np.array([float(v) for v in losses])
 
     jd_option("JD_SEP_WALK", 1)
-    jd_option("JD_SEP_JOINT", 0)
     ref_grad, ref_loss = step(batch=True)
-    jd_option("JD_SEP_JOINT", 1)
-    for batch in (True, False):
-        grad, loss = step(batch)
-        assert np.array_equal(grad, ref_grad), f"batch={batch}"
-        np.testing.assert_allclose(loss, ref_loss, rtol=1e-6)
+    grad, loss = step(batch=False)
+    assert np.array_equal(grad, ref_grad)
+    np.testing.assert_allclose(loss, ref_loss, rtol=1e-6)
     assert np.abs(ref_grad - 0.25).max() > 0
     plan.close()
 

@@ -2,6 +2,8 @@
 """Register / LDS / scratch use of every kernel of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
 
     python tools/kernel_resources.py jolideco_amd/csrc/walkconv.hip [extra hipcc flags]
+
+(the strip-walk kernels are spread over walkconv.hip, walk_adjoint.hip and walk_multi.hip: one run per unit)
 """
 import re
 import subprocess
