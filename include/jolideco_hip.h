@@ -517,6 +517,29 @@ int jd_gmm_prior_jitter_fwd_bwd(jd_gmm* gmm, const float* flux, int H, int W, in
                                 float* value_out, int accumulate_value, float grad_coef, float* grad_flux_accum,
                                 int32_t* argmax_out, const int* shift_dev, void* stream);
 
+/* The PRIOR IMAGE of one draw (priors/patches/core.py:123-151 `prior_image`; the reference's method cannot run as written,
+ * this is the formula its lines state): what the mixture believes the flux looks like.  With N = n(flux) under the handle's
+ * image norm, R0 = roll(N, (shift_y, shift_x)), the patch grid of jd_gmm_prior_fwd_bwd (n_y x n_x patches of P x P pixels,
+ * P = 8 or 16 by the handle), m_ij the mean of patch (i, j) of R0 and k_ij the arg-max component of its mean-free pixels
+ * (ALWAYS the max mode; -1 for a patch the `> -1e5` filter drops),
+ *   R[Y, X]           = sum_{(i, j) covering (Y, X), k_ij >= 0} w[Y - i s, X - j s] (T[k_ij][Y - i s, X - j s] + m_ij),
+ *   image_accum[y, x] = (accumulate ? += : =) scale * n^-1(R[(y + shift_y) mod H, (x + shift_x) mod W]),
+ * w = get_pixel_weights((P, P), stride) (utils/numpy.py:54-79), patches added in ascending (i, j), 0 where no patch covers a
+ * pixel (then n^-1(0)), n^-1 the norm's `inverse` (utils/norms.py) -- np.roll(reco, -shift) followed by norm.inverse.
+ * patch_images: DEVICE table T of K * P * P floats (the caller's choice: the eigen-images of the covariances, the means, ...).
+ * Averaging over n draws is n calls with accumulate = 1 (0 for the first) and scale = 1 / n.
+ * The unchanged max-mode forward pass runs first, into an arg-max buffer of the handle; then two kernels (csrc/gmm_prior_image.hip):
+ * the patch means of the rolled, normed image, and a gather per output pixel with the winners and means of a tile's patches
+ * staged in LDS.  No atomics, a fixed order of the additions: two runs give the same bits.  No host synchronisation; the
+ * work buffers belong to the handle and grow on demand: after the first call for a shape nothing is allocated.
+ * shift_dev as for jd_gmm_prior_fwd_bwd.  D = 64 and D = 256 handles.
+ * JD_ERR_INVALID, nothing launched, the handle usable: a NULL gmm, flux, patch_images or image_accum; an image smaller than a
+ * patch; stride < 1 or stride >= P (the trapezoid's slope is 1 / overlap); a handle whose patch norm is the standardized
+ * one (the formula adds back the mean only). */
+int jd_gmm_prior_image(jd_gmm* gmm, const float* flux, int H, int W, int stride, int shift_y, int shift_x,
+                       const float* patch_images, float scale, float* image_accum, int accumulate,
+                       const int* shift_dev, void* stream);
+
 /* Diagnostics of the screened arg-max path, read without synchronisation from host-mapped memory the last block of a
  * pass writes: out[0..4] = {generation of the last finished pass, it fell back to the dense fp32 kernel (0 / 1), bucket
  * slots its surviving records used, patches it covered, gradient rows per patch the record buffer has room for now}.
@@ -804,7 +827,8 @@ enum {
   JD_KERNEL_POISSON_FUSED = 0,   /* K3: clip + background + Poisson NLL + gradient */
   JD_KERNEL_GMM_FWD = 1,         /* K4: GMM patch log-likelihood, max / logsumexp over components (whole forward pass) */
   JD_KERNEL_GMM_BWD = 2,         /* K4b: per-patch gradient for the selected component(s) */
-  JD_KERNEL_GMM_GATHER = 3,      /* K4c: deterministic overlap-add of the patch gradients */
+  JD_KERNEL_GMM_GATHER = 3,      /* K4c: deterministic overlap-add of the patch gradients; the two launches of
+                                    jd_gmm_prior_image behind its forward pass (patch means + overlap-add of the table) */
   JD_KERNEL_PAD_MUL = 4,         /* K1 */
   JD_KERNEL_CMUL = 5,            /* K2 */
   JD_KERNEL_ADJOINT_EPILOGUE = 6,/* K5 */

@@ -1,4 +1,4 @@
-// Image norms of the GMM patch prior, shared by the 8x8 (gmm_gather.hip) and the 16x16 (gmm256.hip) kernels: n(f), n'(f), the
+// Image norms of the GMM patch prior, shared by the 8x8 (gmm_gather.hip) and the 16x16 (gmm256.hip) kernels: n(f), n^-1(v), n'(f), the
 // argument block of the overlap-add kernels and the chain-rule term they add.  ONE definition of each, so both patch
 // sizes produce the same bits for the same pixel.
 #pragma once
@@ -33,6 +33,21 @@ __device__ __forceinline__ float image_norm_value(float f, const ImageNormArgs& 
   if (KIND == NORM_LOG) return logf(f / nm.p0);
   if (KIND == NORM_POWER) return powf(f / nm.p1, nm.p0);
   return f;
+}
+
+// n^-1(v), the host `inverse` of jolideco_amd/utils/norms.py term by term (the prior image, gmm_prior_image.hip): asinh
+// alpha sinh(v asinh(beta / alpha)); fixed-max v max_value (no clip to undo); sigmoid alpha log(v / (1 - v)) + beta / 2; atan
+// pi / 2 tan(v), WITHOUT alpha as the reference has it; log alpha exp(v); power beta v^(1 / alpha)
+template <int KIND>
+__device__ __forceinline__ float image_norm_inverse(float v, const ImageNormArgs& nm) {
+#pragma clang fp contract(off)
+  if (KIND == NORM_ASINH) return nm.p0 * sinhf(v * nm.c);
+  if (KIND == NORM_FIXED_MAX) return v * nm.p0;
+  if (KIND == NORM_SIGMOID) return nm.p0 * logf(v / (1.f - v)) + nm.p1 / 2.f;
+  if (KIND == NORM_ATAN) return 0.5f * NORM_PI * tanf(v);
+  if (KIND == NORM_LOG) return nm.p0 * expf(v);
+  if (KIND == NORM_POWER) return nm.p1 * powf(v, 1.f / nm.p0);
+  return v;
 }
 
 // n'(f); the kind is uniform over the launch (one scalar branch per call)

@@ -701,6 +701,11 @@ struct jd_gmm {
     if (const int rc = normed.reserve(n)) return rc;
     return want_grad ? staged_grad.reserve(n) : JD_OK;
   }
+  struct PriorImage {  // jd_gmm_prior_image (gmm_prior_image.hip): winner and mean per patch, the value its forward pass leaves
+    jd::DevBuf<int32_t> winner;
+    jd::DevBuf<float> mean;
+    jd::DevBuf<float> value;
+  } prior_image;
   int K = 0;
   bool triangular = true;  // every P_k upper triangular -> zero blocks are skipped
   int n_cu = 256;

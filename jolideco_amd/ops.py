@@ -506,6 +506,7 @@ class GmmHandle:
             check(_hip.lib().jd_gmm_create(K, D, as_fp(pc), as_fp(mp), as_fp(const_k), as_fp(pw), ctypes.byref(handle)))
         self._handle = handle
         self._jitter_ring = None  # (`JitterRing`, made by the first jittered evaluation)
+        self._prior_table = None  # (`prior_image_table`: the host values and their device copy)
         if const_float64 is not None:
             residual = np.ascontiguousarray(np.asarray(const_float64, dtype=np.float64) - const_k.astype(np.float64), dtype=np.float32)
             if residual.shape != (K,):
@@ -622,6 +623,32 @@ class GmmHandle:
         if slot is not None:
             with torch.cuda.device(flux.device):
                 ring.done(slot)
+
+    def prior_image_table(self, patch_images):
+        """The (K, P, P) table of `prior_image` on the handle's device, float32: uploaded once and kept while the caller
+        keeps passing the same values (one table per handle: the eigen-images of the mixture, as a rule)."""
+        patch = 8 if self.D == 64 else 16
+        table = np.ascontiguousarray(patch_images, dtype=np.float32)
+        if table.shape != (self.K, patch, patch):
+            raise ValueError(f"patch_images must have shape ({self.K}, {patch}, {patch}), got {table.shape}")
+        if self._prior_table is None or not np.array_equal(self._prior_table[0], table):
+            self._prior_table = (table.copy(), torch.from_numpy(table).to(self.device))
+        return self._prior_table[1]
+
+    def prior_image(self, flux, stride, shifts, table, out, scale=1.0, accumulate=False, norm=None):
+        """``out (+)= scale *`` the prior image of one draw (jd_gmm_prior_image): every patch of the rolled, normed flux
+        replaced by ``table[arg-max component] + patch mean``, blended with the trapezoid pixel weights, un-rolled and sent
+        through the inverse of ``norm``.  ``table``: (K, P, P) float32 on the flux's device (`prior_image_table`); ``out``:
+        (H, W) float32 there.  Always the max mode and the subtract-mean patch norm; no host synchronisation."""
+        flux, image, shift_dev = self._begin_pass(flux, stride, shifts, norm, None)
+        if isinstance(out, torch.Tensor) and not out.is_contiguous():
+            raise ValueError("out must be contiguous: the kernel writes it in place")
+        table, out = require_hip_tensor(table, "table"), require_hip_tensor(out, "out")
+        patch = 8 if self.D == 64 else 16
+        if table.numel() != self.K * patch * patch or out.numel() != flux.numel():
+            raise ValueError(f"table must hold {self.K} x {patch} x {patch} values and out the image's {flux.numel()}")
+        check(_hip.lib().jd_gmm_prior_image(*image, ptr(table), c_float(scale), ptr(out), int(bool(accumulate)), shift_dev,
+                                            stream_ptr(flux.device)))
 
     def prior_fwd_bwd_step(self, flux, stride, shifts, value_out, value_scale, grad_coef, step, marginalize=False,
                            accumulate_value=False, phases=3, norm=None, patch_norm=None):

@@ -199,6 +199,68 @@ class GMMPatchPrior(Prior):
             marginalize=self.marginalize, phases=phases, norm=self.norm, patch_norm=self.patch_norm,
         )
 
+    def _prior_image_inputs(self, flux, patch_images):
+        """(flux as one HIP image, the table as the handle keeps it) of `prior_image`; every refusal is raised here, before
+        the generator advances."""
+        if self.jitter:
+            raise ValueError("Computing prior images with jittering is not supported.")
+        if self.cycle_spin_subpix:
+            raise NotImplementedError("prior images with cycle_spin_subpix are not implemented: the reference leaves the "
+                                      "sub-pixel un-shift open")
+        if not isinstance(self.patch_norm, SubtractMeanPatchNorm):
+            name = self.patch_norm.to_dict().get("type", type(self.patch_norm).__name__)
+            raise NotImplementedError(f"prior images are not implemented for patch norm {name!r}: the formula adds back "
+                                      "the patch mean only")
+        patch = max(self.patch_shape)
+        if not 1 <= self.stride < patch:
+            raise ValueError(f"a prior image needs overlapping patches: stride {self.stride} is not in [1, {patch - 1}] "
+                             "(the pixel weights' slope is 1 / overlap)")
+        table = self.gmm.eigen_images if patch_images is None else np.asarray(patch_images)
+        if table.shape != (self.gmm.n_components,) + tuple(self.patch_shape):
+            raise ValueError(f"patch_images must have shape {(self.gmm.n_components,) + tuple(self.patch_shape)}, got {table.shape}")
+        if isinstance(flux, torch.Tensor):
+            if not flux.is_cuda:
+                raise RuntimeError("flux must be a HIP tensor or a numpy array: jolideco_amd has no CPU path")
+            image = flux.detach().to(torch.float32)
+        else:
+            image = torch.from_numpy(np.ascontiguousarray(flux, dtype=np.float32)).to(self.device)
+        if image.ndim < 2 or image.numel() != image.shape[-2] * image.shape[-1]:
+            raise ValueError(f"flux must be one image, (H, W) or (1, 1, H, W), got shape {tuple(image.shape)}")
+        image = image.reshape(image.shape[-2:]).contiguous()
+        if image.shape[0] < patch or image.shape[1] < patch:
+            raise ValueError(f"flux {tuple(image.shape)} is smaller than a patch")
+        return image, self.gmm.handle(image.device).prior_image_table(table)
+
+    def prior_image(self, flux, patch_images=None):
+        """What the prior believes ``flux`` looks like, for one draw of the cycle spin (reference:
+        priors/patches/core.py:123-151, which cannot run as written; this is the formula its lines state): every patch of
+        the rolled, normed flux is replaced by the table entry of its best-fitting component plus the patch mean -- the
+        arg-max, also for a prior with ``marginalize=True`` --, the patches are blended with the trapezoid pixel weights, the
+        roll is undone and the image goes through the norm's inverse.  On the device (jd_gmm_prior_image).
+
+        flux : HIP tensor (1, 1, H, W) or (H, W), or numpy (H, W) (uploaded to ``prior.device``).
+        patch_images : optional (K, P, P) array used instead of ``gmm.eigen_images`` -- the component means, samples, ...;
+            unlike the eigen-images such a table does not depend on LAPACK's eigenvector signs.
+
+        One `draw_shifts`: the generator advances as for one evaluation.  Returns a float32 numpy (H, W).  Raises for a
+        jittered prior (ValueError, the reference's own refusal), a sub-pixel cycle spin or the standardized patch norm
+        (NotImplementedError), ``stride == P`` or a table of the wrong shape (ValueError), before anything is drawn."""
+        return self.prior_image_average(flux, n_average=1, patch_images=patch_images)
+
+    def prior_image_average(self, flux, n_average=100, patch_images=None):
+        """The mean of `prior_image` over ``n_average`` draws of the cycle spin (priors/patches/core.py:153-175): accumulated
+        on the device with a fixed order of additions, one copy to the host at the end."""
+        n_average = int(n_average)
+        if n_average < 1:
+            raise ValueError(f"n_average must be at least 1, got {n_average}")
+        image, table = self._prior_image_inputs(flux, patch_images)
+        handle = self.gmm.handle(image.device)
+        out = torch.empty_like(image)
+        for draw in range(n_average):
+            handle.prior_image(image, self.stride, self.draw_shifts(image.shape), table, out, scale=1.0 / n_average,
+                               accumulate=draw > 0, norm=self.norm)
+        return out.cpu().numpy()
+
     def hessian_ones(self, flux):
         """Every patch has its mean subtracted before the mixture sees it, so a constant vector is in the null
         space of each patch's quadratic form: Hessian x ones is exactly zero (the reference's double backward

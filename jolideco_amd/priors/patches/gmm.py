@@ -177,6 +177,7 @@ class GaussianMixtureModel:
         self.registry_name = None
         self.fit_info = None  # set by `fit`
         self._handles = {}
+        self._eigen_images = None  # (`eigen_images`, on first use)
 
     @classmethod
     def from_numpy(cls, means, covariances, weights, meta=None):
@@ -418,6 +419,34 @@ class GaussianMixtureModel:
     def patch_shape(self):
         npix = int(self.means_numpy.shape[-1] ** 0.5)
         return npix, npix
+
+    @property
+    def eigen_images(self):
+        """(K, P, P) float64, cached: per component ``w, v = numpy.linalg.eigh(cov_k)`` in float64 and ``(v @ w)``, the
+        eigenvectors summed with their eigenvalues as weights, as a patch (patches/gmm.py:170-182) -- the default table of
+        `GMMPatchPrior.prior_image`.  The signs of the eigenvectors are LAPACK's, so the table is defined up to them; its
+        norm is not: ``|eigen_image_k|_2 = |cov_k|_F``."""
+        if self._eigen_images is None:
+            images = []
+            for cov in self.covariances_numpy.astype(np.float64):
+                w, v = np.linalg.eigh(cov)
+                images.append((v @ w).reshape(self.patch_shape))
+            self._eigen_images = np.stack(images)
+        return self._eigen_images
+
+    def reduce_to_topk(self, k):
+        """The mixture of the ``k`` components of largest weight, in descending order of weight, with their means and
+        covariances and this model's meta (patches/gmm.py:391-411; the weights are not renormalised, as there)."""
+        idx = np.argsort(self.weights_numpy)[::-1][:k]
+        return self.__class__.from_numpy(
+            means=self.means_numpy[idx], covariances=self.covariances_numpy[idx], weights=self.weights_numpy[idx], meta=self.meta
+        )
+
+    def is_equal(self, other):
+        """The covariances have one shape and are close (`numpy.allclose`): patches/gmm.py:447-452."""
+        if self.covariances_numpy.shape != other.covariances_numpy.shape:
+            return False
+        return bool(np.allclose(self.covariances_numpy, other.covariances_numpy))
 
     # fp32 constants, computed with the same fp32 torch ops as the reference ------------------
     @property
